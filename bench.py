@@ -12,7 +12,17 @@ every rank renders its views, then the per-voxel gradient grid is summed with ON
 exchange step); value = steps / time means the same at every N.  `--scaling weak` (12 views PER rank, a 12*N ring) is
 kept under a different metric string.
 
-The JSON line carries, besides the contract's fields:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) is lean: it sets up, warms up, times the N steps, writes the outputs of the
+last step when `--dump-outputs DIR` is given, and prints ONE result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the config and the dL/dsdf checksum of the last step; `roofline` is null).  Everything else -- the probe launches
+and per-launch statistics behind `roofline`, and every side block below -- runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step: DIR/image.npy (the rendered images of this
+rank's views) and DIR/grad_sdf.npy (dL/dsdf after the step's gradient exchange; DIR/grad_albedo.npy too for sdf_direct_reparam),
+float32.  An array larger than its share of 60 MB is written as a fixed, seeded sample of its flattened elements (the same
+indices in every run), so two builds can be compared file for file.
+
+With `--full` the JSON line carries, besides the contract's fields:
   roofline     -- VALU-issue roofline of the dominant kernel (the primal k_render_items): the path is not HBM-bound (taps
                   are LDS/L1-resident: measured HBM traffic is ~1 % of the algorithmic tap bytes), it issues vector ALU
                   instructions.  achieved = wave-level VALU instructions per launch / launch time; peak = 1024 SIMDs x
@@ -93,6 +103,23 @@ def synth_grid(res, device, n=32, seed=0):
     q = torch.stack([x.abs(), y.abs(), z.abs()], -1) - 0.49
     box = torch.linalg.norm(q.clamp(min=0), dim=-1) + q.max(-1).values.clamp(max=0) - 0.01
     return torch.maximum(sd, box).contiguous()
+
+
+DUMP_BYTES = 60_000_000               # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every (name, tensor) of `arrays` -> <outdir>/<name>.npy in float32.  An array larger than its share of
+    DUMP_BYTES is written as a fixed, seeded sample of its flattened elements (sorted indices, the same in every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    per = DUMP_BYTES // (4 * max(len(arrays), 1))
+    for k, (name, t) in enumerate(arrays):
+        t = t.detach().float()
+        if t.numel() > per:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(k)).narrow(0, 0, per).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(outdir, name + '.npy'), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32))
 
 
 def cpu_baseline(args, target_seconds=15.0):
@@ -471,18 +498,27 @@ def main():
     ap.add_argument('--spp-grad', type=int, default=64)
     ap.add_argument('--integrator', default='sdf_silhouette_reparam')
     ap.add_argument('--scaling', choices=('strong', 'weak'), default='strong')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline (probe launches, per-launch statistics) and the side blocks cpu_baseline, '
+                         'low_spp, direct, opt_iteration, scaling_prediction')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="write the last timed step's images and gradients to DIR/<name>.npy (float32, < 64 MB in all)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-low-spp', action='store_true')
     ap.add_argument('--no-direct', action='store_true')
     ap.add_argument('--no-opt-iteration', action='store_true')
     ap.add_argument('--no-scaling-prediction', action='store_true')
-    ap.add_argument('--emulate-rank', default='', help="r/N: time rank r's shard of an N-GPU strong-scaling run alone on this GPU (scaling_prediction)")
+    ap.add_argument('--emulate-rank', default='', help="r/N (with --full): time rank r's shard of an N-GPU strong-scaling run alone on this GPU (scaling_prediction)")
     ap.add_argument('--overlap', type=int, default=1, help='1: primal pass and gradient sweep on two HIP streams (dsdf.render_step)')
     ap.add_argument('--partition', choices=('cost', 'uniform'), default='cost',
                     help="multi-rank strong scaling: 'cost' = parallel.cost_partition of the row costs the ranks measured in the previous step "
                          "(per-pixel proof flags, one 25 KB all-reduce per step); 'uniform' = round-robin views / even row windows")
     ap.add_argument('--child', action='store_true', help='(internal) the measuring process of a supervised single-GPU run')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.emulate_rank and not args.full:
+        ap.error('--emulate-rank is part of the scaling_prediction block: it needs --full')
     if int(os.environ.get('WORLD_SIZE', 1)) == 1 and not args.child and os.environ.get('BENCH_INPROCESS') != '1':
         sys.exit(supervise(sys.argv[1:]))
     import faulthandler
@@ -557,6 +593,8 @@ def main():
     trackers = {}                               # (spp pair) -> parallel.CostTracker: the row costs all ranks agreed on after the last step
     step_events = {}                            # (spp pair) -> HIP events around this rank's last step
     pending = [None, None]                      # work handles of the all-reduces in flight, per gradient buffer
+    last_it = args.warmup + args.steps - 1      # the last timed step: its images are kept for --dump-outputs
+    last_images = {}
 
     def make_step(spp_p, spp_g, prim_ms, grad_ms):
         def step(it, timed):
@@ -585,11 +623,13 @@ def main():
                     part = trackers[key].partition()
                 t0, t1 = ev(), ev()
                 t0.record()
-                _, work = parallel.render_step(ops, args.views, args.img, args.img, rank, world,
-                                               lambda im, views: torch.sign(im - tgt[views]) * scale, grad, extra_grads=extra,
-                                               gather_images=False, async_reduce=True, force_reduce=dist is not None, partition=part)
+                imgs, work = parallel.render_step(ops, args.views, args.img, args.img, rank, world,
+                                                  lambda im, views: torch.sign(im - tgt[views]) * scale, grad, extra_grads=extra,
+                                                  gather_images=False, async_reduce=True, force_reduce=dist is not None, partition=part)
                 t1.record()
                 pending[b] = work
+                if timed and it == last_it:
+                    last_images['image'] = imgs        # (this rank's pixel rows filled; the whole images at world 1)
                 if part is not None:
                     # what this step's proofs say about the work per row, and how long the PREVIOUS step took on this rank (its events
                     # have completed; this step's have not) -> the next step's partition.  One small collective.
@@ -604,9 +644,9 @@ def main():
                 if args.overlap:
                     # primal render and the forward sweep of the gradient pass on two HIP streams (dsdf.render_step)
                     e0.record()
-                    dsdf.render_step(grid, sensors, spp_p, spp_g, lambda im: torch.sign(im - tgt) * scale, grad, seeds,
-                                     [x + 1 for x in seeds], integrator=args.integrator, shading=shade.get('shading'),
-                                     grad_albedo=galb)
+                    img = dsdf.render_step(grid, sensors, spp_p, spp_g, lambda im: torch.sign(im - tgt) * scale, grad, seeds,
+                                           [x + 1 for x in seeds], integrator=args.integrator, shading=shade.get('shading'),
+                                           grad_albedo=galb)
                     e1.record(); e2.record()
                 else:
                     e0.record()
@@ -618,6 +658,8 @@ def main():
                     e2.record()
                 if timed:
                     prim_ms.append((e0, e1)); grad_ms.append((e1, e2))
+                    if it == last_it:
+                        last_images['image'] = img
             if dist is not None:
                 pending[b] = parallel.all_reduce_gradients([grad] + extra, async_op=True, force=True)
         return step
@@ -653,9 +695,17 @@ def main():
     elapsed = timed_run(make_step(args.spp_primal, args.spp_grad, prim_ms, grad_ms), args.warmup, args.steps)
     # dL/dsdf of the last timed step (summed over ranks): must agree at every N up to the order of the float atomics
     grad_l1 = float(grads[(args.warmup + args.steps - 1) & 1].double().abs().sum())
+    mark(f'timed region done: {1e3 * elapsed / args.steps:.2f} ms/step')
+    if args.dump_outputs and rank == 0:
+        # (before the --full probes below, which render into the same gradient buffers)
+        b = last_it & 1
+        dump_outputs(args.dump_outputs, ([('image', last_images['image'])] if last_images.get('image') is not None else []) +
+                     [('grad_sdf', grads[b])] + ([('grad_albedo', galbs[b])] if galbs[b] is not None else []))
+        mark(f'outputs of the last timed step written to {args.dump_outputs}')
+    last_images.clear()
     kern_p, kern_g = [], []
-    mark(f'timed region done: {1e3 * elapsed / args.steps:.2f} ms/step; probe launches')
-    if nv and not tiled:
+    if args.full and nv and not tiled:
+        mark('probe launches')
         # the roofline needs the dominant kernel's OWN launch time: in the timed region above it shares the chip with the
         # gradient sweep of the other stream, so a few calls are timed alone afterwards, same process, same inputs -- the whole
         # call with HIP events on the launch stream (prim_ms / grad_ms), the RENDER KERNEL inside it with the library's
@@ -682,8 +732,8 @@ def main():
 
     # per-launch statistics (untimed; same launch shape as the timed ones)
     out_cfg, roof = {}, None
-    mark('per-launch statistics')
-    if nv and not tiled:
+    if args.full and nv and not tiled:
+        mark('per-launch statistics')
         st_p, st_g = dsdf.new_stats(dev), dsdf.new_stats(dev)
         galb = galbs[0]
         dsdf.render_forward(grid, sensors, args.spp_primal, seeds=list(range(nv)), integrator=args.integrator, stats=st_p, **shade)
@@ -801,7 +851,7 @@ def main():
     }
 
     # THE HEADLINE FIRST (a stall in a side block must not lose the measurement).  The line is printed and flushed
-    # here, right after the timed region and its probe launches; every side block that completes re-prints the enriched line (the
+    # here, right after the timed region (and, with --full, its probe launches); every side block that completes re-prints the enriched line (the
     # driver parses the last one).  A side block that raises is recorded as {"error": ...}; one that would start after the
     # wall-clock budget is recorded as {"skipped": "budget"}; a block that never returns is the supervisor's business (main()).
     def emit():
@@ -813,7 +863,7 @@ def main():
     budget = float(os.environ.get('BENCH_BUDGET_S', 150))
 
     def side(name, fn, enabled=True):
-        if not enabled:
+        if not (args.full and enabled):                       # (a plain run ends with the headline)
             return
         if dist is None and time.time() - _T0 > budget:      # (one rank only: ranks must not disagree about a collective block)
             out[name] = {"skipped": "budget", "budget_s": budget}

@@ -225,3 +225,24 @@ def test_bench_supervisor_relays_retries_and_aborts(tmp_path, monkeypatch):
     assert rc == 0 and starts == 2 and 'low_spp' in rows[-1]
     rc, rows, starts = run('stall_after_headline')
     assert rc == 0 and starts == 1 and rows[-1]['value'] == 1.0 and 'aborted' in rows[-1] and 'low_spp' not in rows[-1]
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files; an array within its share of DUMP_BYTES is written whole, a larger one
+    as a seeded sample of its elements -- the same indices in every call, all files together within DUMP_BYTES."""
+    import importlib.util
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8000)
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    big = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), [('small', small), ('big', big)])
+    for d in ('a', 'b'):
+        s, b = np.load(tmp_path / d / 'small.npy'), np.load(tmp_path / d / 'big.npy')
+        assert s.dtype == np.float32 and s.shape == (2, 3) and (s == small.numpy()).all()
+        assert b.dtype == np.float32 and b.shape == (1000,) and len(np.unique(b)) == 1000 and (np.diff(b) > 0).all()
+        assert sum(os.path.getsize(tmp_path / d / f) for f in ('small.npy', 'big.npy')) <= 8000 + 2 * 128
+    assert (np.load(tmp_path / 'a' / 'big.npy') == np.load(tmp_path / 'b' / 'big.npy')).all()

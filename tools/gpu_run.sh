@@ -6,7 +6,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0 PYTHONFAULTHANDLER=1
 JOB=${1:-bench}; TAG=${2:-$JOB}
 O=gpurun_out/$TAG; mkdir -p $O
 find . -name "*.so" | xargs touch
-DRIVER="python3 bench.py --gpus 1 --steps 20 --warmup 5"
+DRIVER="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"   # (--full: roofline + every side block)
 run() {  # run <name> <timeout> <cmd...>: stdout -> $O/<name>.out, stderr -> $O/<name>.err, wall clock + rc -> $O/<name>.rc
   local name=$1 to=$2; shift 2
   local t0=$(date +%s.%N)
@@ -85,7 +85,7 @@ case $JOB in
     python profiles/summarize_pmc.py $TAG $O $O/pmc_stats.json > $O/summarize_pmc.log 2>&1; tail -4 $O/summarize_pmc.log | cut -c1-600
     run bench 600 $DRIVER; tail -1 $O/bench.out > $O/bench.json
     run bench_seq 300 $DRIVER --overlap 0 --no-cpu-baseline --no-direct --no-opt-iteration --no-scaling-prediction
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-low-spp --no-direct --no-opt-iteration --no-scaling-prediction > $O/trace.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-low-spp --no-direct --no-opt-iteration --no-scaling-prediction > $O/trace.log 2>&1
     f=$(find $O/trace -name "t_kernel_stats.csv" | head -1); k=$(find $O/trace -name "t_kernel_trace.csv" | head -1)
     [ -n "$f" ] && python profiles/summarize.py $TAG $f $k > $O/summarize.log 2>&1
     [ -n "$k" ] && python tools/step_timeline.py $k > profiles/${TAG}_step_timeline.md 2> $O/step_timeline.err
