@@ -64,3 +64,65 @@ def oracle_direct(case, extra, reparam=True, hide_emitters=False, grads=False, p
         return img
     (img * case['grad_image'].double()).sum().backward()
     return img.detach(), data.grad, alb.grad
+
+
+# Ragged shapes (Z, Y, X): x sizes at every residue mod 4 (the row-block copy's x chunks are 4 taps apart), y / z sizes that are not
+# multiples of 8 (partial last blocks of the 8^3 / 4^3 / 2^3 proof bounds), a side thinner than one 8^3 block; films whose sides
+# leave partial work-list tiles.  name: (shape, W, H, spp, n_cams, views, seed)
+RAGGED = {
+    'rag_x1': ((37, 30, 45), 45, 31, 64, 6, (0, 2, 4), 41),        # rx % 4 == 1
+    'rag_x2': ((26, 41, 34), 33, 47, 64, 6, (1, 4), 42),           # rx % 4 == 2
+    'rag_x3': ((51, 19, 23), 45, 31, 64, 6, (0, 3), 43),           # rx % 4 == 3
+    'rag_thin': ((10, 6, 39), 41, 29, 64, 6, (1, 3, 5), 44),       # y and z sides under one 8^3 block
+}
+
+
+def ragged_grid(shape, seed, walls=True):
+    """Seeded union of spheres sampled on per-axis linspace (voxel sizes differ per axis), rounded to fp32 and returned as fp64.
+    walls=True: sphere 0 crosses the +x and +y faces of the unit box, so that the cells of the last x chunk and of the partial blocks
+    hold surface; sphere 1 crosses the +x face near z = 0.  walls=False: the same two spheres moved inwards until they stop 0.6 of a
+    voxel short of those faces -- the surface still runs through the last cell of each axis, but never meets a wall of the box
+    (where it does, the warp field's 1/denom^3 weights of the grazing samples along the crease make the fp32 gradient a heavy-tailed
+    draw: tests/test_gpu_ragged.py, DESIGN.md)."""
+    rng = np.random.default_rng(seed)
+    lin = [np.linspace(0, 1, n) for n in shape]
+    z, y, x = np.meshgrid(*lin, indexing='ij')
+    pts = np.stack([x, y, z], -1)
+    rz, ry, rx = shape
+    z0, y1 = rng.uniform(0.4, 0.6), rng.uniform(0.3, 0.5)
+    if walls:
+        spheres = [((0.93, 0.9, z0), 0.2), ((0.97, y1, 0.1), 0.14)]
+    else:
+        spheres = [((0.8 - 0.6 / (rx - 1), 0.8 - 0.6 / (ry - 1), z0), 0.2), ((0.86 - 0.6 / (rx - 1), y1, 0.14 + 0.6 / (rz - 1)), 0.14)]
+    spheres += [(tuple(rng.uniform(0.3, 0.7, 3)), rng.uniform(0.1, 0.2)) for _ in range(3)]
+    sd = np.full(tuple(shape), 1e9)
+    for c, r in spheres:
+        sd = np.minimum(sd, np.linalg.norm(pts - np.asarray(c), axis=-1) - r)
+    return torch.tensor(sd.astype(np.float32)).double()
+
+
+def ragged_case(name, spp=None, walls=True):
+    """A make_case dict (view 0 of the case) for a ragged grid and film, plus `views`: one such dict per view of the ring (its own
+    cam, offsets and grad_image slice; `name` carries the view), and `offsets` / `grad_image` of all views concatenated in view
+    order under `offsets_all` / `grad_image_all` -- what one multi-view call of the HIP path takes.  `spp` overrides the case's
+    sample count, walls=False moves the surface off the box walls (ragged_grid); the name then carries either (precision.py caches
+    by name)."""
+    shape, W, H, spp0, ncam, icams, seed = RAGGED[name]
+    grid = ragged_grid(shape, seed, walls)
+    if not walls:
+        name = f'{name}_inner'
+    if spp is not None and spp != spp0:
+        name, seed = f'{name}_spp{spp}', seed + spp
+    spp = spp or spp0
+    gen = torch.Generator().manual_seed(seed)
+    origins = O.regular_camera_origins(ncam)
+    views = []
+    for k, icam in enumerate(icams):
+        offsets = torch.rand((W + 4) * (H + 4) * spp, 2, generator=gen, dtype=torch.float32)
+        grad_image = torch.randn(H, W, 3, generator=gen, dtype=torch.float32)
+        views.append(dict(name=f'{name}_v{icam}', grid=grid, ncam=ncam, icam=icam, origin=origins[icam],
+                          cam=O.Camera(origins[icam]).rounded(), W=W, H=H, spp=spp, offsets=offsets, grad_image=grad_image))
+    case = dict(views[0], name=name, views=views, icams=list(icams))
+    case['offsets_all'] = torch.cat([v['offsets'] for v in views])
+    case['grad_image_all'] = torch.stack([v['grad_image'] for v in views])
+    return case

@@ -58,21 +58,45 @@ def c_backward(case, integ, reparam=True, double=True):
                                     case['grad_image'].numpy(), integ, reparam)
 
 
-def image_rel_l2_but_flips(img, ref, tol, max_flips=2):
+def image_rel_l2_but_flips(img, ref, tol, spp, max_flips=2, env=None):
     """rel-L2 of an image against the oracle's, setting aside at most `max_flips` 5 x 5 pixel windows: a sample whose ray grazes
     the surface within the trace epsilon hits in one fp32 evaluation and misses in another (the hit-count check of the primal allows
     `a handful` for the same reason), and ONE such sample is 1 / spp of a pixel -- 1.5e-4 of a 128 x 128 image at spp 64 -- spread over
-    the 4 x 4 footprint of its Gaussian splat.  Returns (plain, rest, windows set aside)."""
+    the 4 x 4 footprint of its Gaussian splat.  A window is set aside only if it can be such a flip:
+      - its squared error is at most the most one sample can move: the sample changes pixel p by w_p |df| / W_p per channel, with
+        w_p <= 1 (the filter's peak) and W_p (the filter weights the pixel collects) ~ (sigma sqrt(2 pi))^2 spp = 1.57 spp for
+        sigma = 0.5 px -- taken as spp, and |df| <= the reference's value range (largest over the channels): at most
+        (range / spp)^2 per pixel and channel, over the 4 x 4 pixels the filter's radius of 2 px reaches:
+            removed <= 16 * channels * (range / spp)^2
+      - it does not touch the film border (border pixels also collect the splats of the 2-pixel apron's samples: an error there is
+        not shaped like one interior sample)
+      - with `env` (the constant environment radiance of sdf_direct_reparam) it holds no env-filled pixel (every sample missed:
+        its value is exact in any precision, an error there is not a grazing hit).  No GPU test passes `env` yet -- the direct
+        integrator's images are gated on the plain rel-L2 -- so this branch is exercised by tests/test_precision_host.py only
+    The first window that fails these stops the search.  Returns (plain, rest, windows): `windows` lists the windows set aside as
+    dicts (y, x, removed, bound) for P.record."""
     img = np.asarray(img, np.float64); ref = np.asarray(ref, np.float64)
+    H, W, nc = ref.shape
     e2 = ((img - ref) ** 2).sum(-1)
     den = max((ref ** 2).sum(), 1e-300)
     plain = float(np.sqrt(e2.sum() / den))
-    work, n = e2.copy(), 0
-    while np.sqrt(work.sum() / den) >= tol and n < max_flips:
+    rng = float((ref.reshape(-1, nc).max(0) - ref.reshape(-1, nc).min(0)).max())
+    bound = 16.0 * nc * (rng / spp) ** 2
+    env_px = None
+    if env is not None:
+        env_px = (np.abs(ref - np.asarray(env, np.float64)) <= 1e-6 * np.abs(np.asarray(env, np.float64)).max()).all(-1)
+    work, windows = e2.copy(), []
+    while np.sqrt(work.sum() / den) >= tol and len(windows) < max_flips:
         y, x = np.unravel_index(int(np.argmax(work)), work.shape)
-        work[max(y - 2, 0):y + 3, max(x - 2, 0):x + 3] = 0.0
-        n += 1
-    return plain, float(np.sqrt(work.sum() / den)), n
+        sl = (slice(max(y - 2, 0), y + 3), slice(max(x - 2, 0), x + 3))
+        removed = float(work[sl].sum())
+        if removed > bound or y - 2 <= 0 or x - 2 <= 0 or y + 2 >= H - 1 or x + 2 >= W - 1:
+            break
+        if env_px is not None and env_px[sl].any():
+            break
+        work[sl] = 0.0
+        windows.append(dict(y=int(y), x=int(x), removed=removed, bound=bound))
+    return plain, float(np.sqrt(work.sum() / den)), windows
 
 
 def trimmed_rel_l2(a, b, frac=0.01):

@@ -62,9 +62,9 @@ def test_config_size_parity(dsdf, name, integ):
     r = P.reference_gradient(case, integ, True)
     # (the gradient pass builds its camera rays with the IEEE sequences since round 6: an eps-grazing sample may flip against the
     # fp64 oracle like in the primal's hit count above -- at most two sample footprints may be set aside)
-    e_plain, e_rest, flips = P.image_rel_l2_but_flips(gimg[0].cpu().numpy(), r['img64'], FWD_TOL)
-    P.record('image_grad_pass', case=name, integ=integ, err=e_plain, err_rest=e_rest, flips=flips)
-    assert e_rest < FWD_TOL, (e_plain, e_rest, flips)
+    e_plain, e_rest, windows = P.image_rel_l2_but_flips(gimg[0].cpu().numpy(), r['img64'], FWD_TOL, case['spp'])
+    P.record('image_grad_pass', case=name, integ=integ, err=e_plain, err_rest=e_rest, flips=len(windows), windows=windows)
+    assert e_rest < FWD_TOL, (e_plain, e_rest, windows)
     ok, msg = P.check_gradient('config', case, integ, True, gg.cpu().numpy(), config_size=True)
     print(msg)
     assert ok, msg

@@ -472,16 +472,22 @@ def test_hit_proof_is_exact(dsdf, spp):
     assert rel_l2(ga.cpu(), gb.cpu()) < 1e-5
 
 
-@pytest.mark.parametrize('name', ['sphere64', 'blob64_flat'])
+@pytest.mark.parametrize('name', ['sphere64', 'blob64_flat', 'rag_x3'])
 def test_device_proof_flags_match_host_proof(dsdf, harness, name):
     """The flags the device computes (k_pixel_skip + the wave-cooperative k_pixel_hit_fine, read back through the buffer of
     dsdf_share_pixel_skip) against the serial host form of the same proofs (dsdf_proof.h through tests/harness) -- and every pixel
-    the DEVICE flags 'all samples hit' / 'empty' against rays traced by the host build of the march."""
+    the DEVICE flags 'all samples hit' / 'empty' against rays traced by the host build of the march.  rag_x3 (51 x 19 x 23, tests/cases.py):
+    partial last blocks on every axis of the 8^3 / 4^3 minima and the 2^3 maxima; its film is fine enough for the hit proof."""
     import ctypes as C
-    from test_proof_host import _grids, PX_EMPTY, PX_HIT
+    from test_proof_host import _grids, PX_EMPTY, PX_HIT, RAGGED_FILMS
+    from cases import RAGGED, ragged_grid
     from dsdf import _lib
-    grid_np = _grids()[name]
-    W = H = 176
+    if name in RAGGED:
+        grid_np = ragged_grid(RAGGED[name][0], RAGGED[name][-1]).float().numpy()
+        W, H = RAGGED_FILMS[name][0]
+    else:
+        grid_np = _grids()[name]
+        W = H = 176
     icam = 2
     origin = O.regular_camera_origins(5)[icam]
     cam = O.Camera(origin).params()

@@ -112,3 +112,43 @@ def test_hit_proof_survives_a_noisy_field(harness):
     cam = O.Camera(O.regular_camera_origins(5)[1]).params()
     flags, info, hits = _check(harness, grid, cam, 176, 176, spp=6)
     print(f"noisy sphere: {((flags & PX_HIT) != 0).sum()} of {hits.all(-1).sum()} all-hit pixels proven")
+
+
+# films (W, H) per ragged grid: 'fine' is fine enough for the 4^3 minima and -- but on the thin grid, which would need a film of ~1000^2
+# (hit_step: lateral spread <= 0.01 x the SHORTEST side) -- for the hit proof and its fine stage; 'coarse' leaves the 8^3 minima only
+RAGGED_FILMS = {'rag_x1': ((240, 234), (45, 38)), 'rag_x2': ((252, 246), (41, 34)), 'rag_x3': ((420, 414), (51, 44)),
+                'rag_thin': ((86, 80), (39, 32))}
+
+
+# (name, film, icam): cameras of the 6-ring for which the proofs flag a good number of pixels (a case that flags nothing proves
+# nothing).  rag_thin gets no 'coarse' case: its 8^3 minima, dilated by one block, cover the whole 6-voxel y side and 10-voxel z side,
+# so every window holds surface and no pixel is provably empty.
+RAGGED_PROOF_CASES = [('rag_x1', 'fine', 0), ('rag_x1', 'fine', 3), ('rag_x2', 'fine', 0), ('rag_x2', 'fine', 3), ('rag_x3', 'fine', 0),
+                      ('rag_x3', 'fine', 3), ('rag_thin', 'fine', 2), ('rag_thin', 'fine', 4), ('rag_x1', 'coarse', 2),
+                      ('rag_x1', 'coarse', 5), ('rag_x2', 'coarse', 1), ('rag_x2', 'coarse', 5), ('rag_x3', 'coarse', 0), ('rag_x3', 'coarse', 1)]
+
+
+@pytest.mark.parametrize('name,film,icam', RAGGED_PROOF_CASES)
+def test_proofs_agree_with_traced_rays_on_ragged_grids(harness, name, film, icam):
+    """Grid sides that are not multiples of the 8^3 / 4^3 / 2^3 proof blocks (partial last blocks, tests/cases.py RAGGED), with
+    surface up to the +x / +y faces: every pixel flagged empty or all-hit agrees with the traced samples."""
+    from cases import RAGGED, ragged_grid
+    shape, seed = RAGGED[name][0], RAGGED[name][-1]
+    grid = ragged_grid(shape, seed).float().numpy()
+    W, H = RAGGED_FILMS[name][film == 'coarse']
+    cam = O.Camera(O.regular_camera_origins(6)[icam]).params()
+    flags, info, hits = _check(harness, grid, cam, W, H, spp=6, seed=31 + icam)
+    hit_px, empty_px = (flags & PX_HIT) != 0, (flags & PX_EMPTY) != 0
+    assert not (hit_px & empty_px).any()
+    # info: [0] step of the empty-space proof, [1] step of the hit proof, [2] coarse level (1: 4^3 minima, 0: 8^3), [3] step of the
+    # hit proof's fine stage; a step of 0 = that proof is off for this film
+    assert info[0] > 0 and info[2] == (1 if film == 'fine' else 0), info
+    if film == 'coarse':
+        assert info[1] == 0, info                                             # too coarse for the hit proof
+        assert empty_px.sum() >= 50, empty_px.sum()
+    elif name == 'rag_thin':
+        assert info[1] == 0, info           # hit proof off: lateral spread <= 0.01 x the SHORTEST side needs a film of ~1000^2 here
+        assert empty_px.sum() >= 500, empty_px.sum()
+    else:
+        assert info[1] > 0 and info[3] > 0, info                              # hit proof and its fine stage on
+        assert empty_px.sum() >= 5000 and hit_px.sum() >= 500, (empty_px.sum(), hit_px.sum())
