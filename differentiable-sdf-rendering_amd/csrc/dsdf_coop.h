@@ -12,20 +12,8 @@
 // dependent chain of a step shrinks from ~200 to ~80 instructions (value only) and from ~900 to ~350 (Hessian march).
 #pragma once
 
-#ifndef DSDF_COOP
-#define DSDF_COOP 3                 /* k_render_pass: bit 0 value-only traces, bit 1 differentiable traces.  12 views x 512^2 of the 256^3 bench
-                                       grid, same box: 4-spp primal call 2.47 -> 2.38 ms, 1-spp gradient call 3.47 -> 3.10 ms, the 4 / 1-spp step
-                                       4.15 -> 4.01 ms, the 16 / 4-spp step 9.71 -> 9.53 ms (profiles/r05_ab.md, r05s / r05t).  The first build kept
-                                       the lock-step phase's registers alive (175 / 217 VGPRs instead of 105 / 137, i.e. 2 waves per SIMD
-                                       instead of 4 / 3) and LOST 68 % / 15 %: the bulk of a low-spp pass is throughput. */
-#endif
-#ifndef DSDF_COOP_TAIL
-#define DSDF_COOP_TAIL 0            /* tail kernels (dsdf_tail.h), once their queues are drained: bit 0 k_tail_trace_plain, bit 1 k_tail_trace_diff.
-                                       Measured (r05t): bit 0 takes 26 % of the primal tail's wave steps away and 0.1 ms (0.5 %) off the primal
-                                       call, nothing off the step; bit 1 costs the step 1.4 ms (the kernel grows from 206 to 256 VGPRs and runs
-                                       beside the primal workers) and makes the sweep's rounding depend on which rays are left when the queue
-                                       drains -- run-to-run differences of 1e-5 in dL/dsdf.  Both stay off. */
-#endif
+// k_render_pass traces its primary rays this way (both passes); the tail kernels do not (measured no gain, and the
+// sweep's rounding would depend on which rays are left when its queue drains).
 #ifndef DSDF_COOP_RAYS
 #define DSDF_COOP_RAYS 4            /* rays per wave in the cooperative phase (16 lanes each) */
 #endif

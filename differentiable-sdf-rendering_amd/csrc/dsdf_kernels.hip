@@ -581,9 +581,8 @@ __global__ __launch_bounds__(DSDF_BLOCK) void k_render_pass(GridView G, dsdf_par
     Lane L;
     const bool windowed = M.tile_w && __ballot(!far) != 0;       // (a wave of far pixels touches nothing)
     if (windowed) tile_window_clear<NCH>(TW, lid);
-#if DSDF_COOP
     // the primary rays of the wave, traced at wave level (dsdf_coop.h: the last rays get 16 lanes each)
-    constexpr bool COOP = !DIRECT && ((DSDF_COOP >> (DIFF ? 1 : 0)) & 1);        // bit 0: plain traces, bit 1: differentiable traces
+    constexpr bool COOP = !DIRECT;
     if (COOP) {
         const bool on = !far && !known_hit && !skip_trace;
         if (!far) L = lane_setup<!DIFF>(A, P, lane);
@@ -593,9 +592,6 @@ __global__ __launch_bounds__(DSDF_BLOCK) void k_render_pass(GridView G, dsdf_par
             else coop_trace_plain(G, P, L.ray.o, L.ray.d, L.ray.maxt, on, tr, lid);
         }
     }
-#else
-    constexpr bool COOP = false;
-#endif
     if (!far) {
         if (!COOP) L = lane_setup<!DIFF>(A, P, lane);
         if (known_hit) tr.its_t = 0.f;
@@ -803,11 +799,10 @@ __global__ __launch_bounds__(64, DIRECT ? DSDF_BWD_DIRECT_MINWAVES : DSDF_BWD_MI
 // on the sweep's stream while the primal pass is still busy -- and k_backward_apply once the image gradient exists: film-adjoint
 // gather, 30 FMAs, transposed scatter (lane_backward_coef / _apply, dsdf_lane.h).  (The fused k_backward is 3.5 ms of dependent
 // chains at 1.4 waves/SIMD, exposed at the end of every step.)
-// Two launches per sweep: the FIRST right behind the render kernel, for the samples it queued itself (`mark` receives the
-// count of every unit as it stood) -- it runs while the primal workers still have the chip, ahead of the tail kernel, which on
-// the step's critical path only needs the time of its longest rays once the primal kernel is gone; the SECOND after the tail
-// kernel, for the few samples that appended (`from` = the marks).  (One launch behind the tail kernel: +1.1-1.5 ms at the end of
-// every step, profiles/r04_step_timeline.md.)
+// Two launches per sweep: the FIRST on a helper stream beside the tail kernel, for the samples the render kernel queued itself
+// (`upto` = a copy of every unit's count as the render kernel left it); the SECOND after the tail kernel, for the few samples it
+// appended (`from` = the same copy).  (One launch behind the tail kernel: +1.1-1.5 ms at the end of every step,
+// profiles/r04_step_timeline.md.)  The host passes no `mark` (a launch ahead of the tail kernel that took the copy itself).
 #ifndef DSDF_COEF_MINWAVES
 #define DSDF_COEF_MINWAVES 1
 #endif
@@ -839,21 +834,10 @@ __global__ __launch_bounds__(64, DSDF_COEF_MINWAVES) void k_backward_coef(GridVi
     }
 }
 
-// DSDF_APPLY_HALF_TILE (default 1): the scatter of k_backward_apply goes through the 9 KB half tile (wave_scatter_half), 0: the 17 KB
-// tile of the fused kernel.
-#ifndef DSDF_APPLY_HALF_TILE
-#define DSDF_APPLY_HALF_TILE 1
-#endif
-#if DSDF_APPLY_HALF_TILE
-#define DSDF_APPLY_TILE_FLOATS DSDF_SCATH_FLOATS
-#define DSDF_APPLY_SCATTER wave_scatter_half
-#else
-#define DSDF_APPLY_TILE_FLOATS DSDF_SCAT_FLOATS
-#define DSDF_APPLY_SCATTER wave_scatter_t
-#endif
+// (the scatter of k_backward_apply goes through the 9 KB half tile, wave_scatter_half, not the 17 KB tile of the fused kernel)
 __global__ __launch_bounds__(64) void k_backward_apply(GridView G, dsdf_params P, ViewBatch VB, Queue qall,
                                                        const float *__restrict__ block_adjs, float *__restrict__ grad_grid) {
-    __shared__ __attribute__((aligned(16))) float tile[DSDF_APPLY_TILE_FLOATS];
+    __shared__ __attribute__((aligned(16))) float tile[DSDF_SCATH_FLOATS];
     const ViewArgs &A = VB.v[blockIdx.y];
     const float *__restrict__ block_adj = block_adjs + (size_t)blockIdx.y * 2 * A.Wb * A.Hb;
     const Queue q = view_queue(qall, blockIdx.y);
@@ -884,8 +868,8 @@ __global__ __launch_bounds__(64) void k_backward_apply(GridView G, dsdf_params P
             const Lane L = lane_setup(A, P, lane);
             lane_backward_apply(P, A, L, tr, c, block_adj, req);
         }
-        DSDF_APPLY_SCATTER(G, grad_grid, req[0], tile, lid);
-        if (A.integrator != DSDF_SILHOUETTE) DSDF_APPLY_SCATTER(G, grad_grid, req[1], tile, lid);
+        wave_scatter_half(G, grad_grid, req[0], tile, lid);
+        if (A.integrator != DSDF_SILHOUETTE) wave_scatter_half(G, grad_grid, req[1], tile, lid);
     }
 }
 
@@ -952,8 +936,9 @@ static void pass_shape(int W, int H, int spp, int &tile_w, int &tile_h, size_t &
     nunits = (waves + 3) / 4 * 4;
 }
 
-// A launch of up to DSDF_MAX_BATCH views is cut into at most DSDF_MAX_GROUPS view groups, one render-kernel launch each,
-// so that the tail kernel of a group (latency-bound: its longest rays) runs beside the render kernel of the next group.
+// The work-list headers and the tail queues of a workspace are carved as DSDF_MAX_GROUPS slices, a tail slice sized for
+// `group_views` views; a launch of nv views uses the first ceil(nv / group_views) tail slices together, as one queue.  (The
+// layout is ABI: dsdf_*_workspace_size.)
 #define DSDF_MAX_GROUPS 4
 
 struct Workspace {
@@ -1244,8 +1229,8 @@ size_t dsdf_forward_workspace_size(int width, int height, int spp, int n_views, 
 
 }  // extern "C" (the shared host plumbing below is C++)
 
-// One batch of views of a render call: view arguments, empty-space proof, the render pass (primal or gradient sweep)
-// into ws.block.  Everything is enqueued on `st`.
+// One batch of views of a render call: view arguments, per-pixel proofs, the render pass (primal or gradient sweep) into
+// ws.block.  Everything is enqueued on `st`.
 struct PassCtx {
     const float *padded; int rx, ry, rz; const dsdf_params *prm; dsdf_params pp;
     int W, H, spp, integrator, flags; bool direct;
@@ -1255,9 +1240,9 @@ struct PassCtx {
     float *film;           // caller-owned film block to ACCUMULATE into (tile calls), or nullptr: the workspace's, zeroed
     size_t ws_bytes;       // the caller's workspace (what lies behind the carved part may hold the cell table of the direct primal)
     hipStream_t st;
-    bool coef_early;       // gradient sweep: launch k_backward_coef for the render kernel's own samples AHEAD of the tail kernel
-    bool coef_beside;      // ... or BESIDE the tail kernel, on the other helper stream, up to a snapshot of the queue lengths (DSDF_COEF_EARLY=2)
-    bool coef_done_early;  // (set by run_pass when it did either)
+    bool coef_beside;      // gradient sweep: k_backward_coef for the render kernel's own samples BESIDE the tail kernel, on a helper
+                           // stream, up to a snapshot of the queue lengths
+    bool coef_done_early;  // (set by run_pass when it did)
 };
 
 static PassCtx make_ctx(const float *padded, int rx, int ry, int rz, const dsdf_params *prm, int W, int H, int spp,
@@ -1275,8 +1260,18 @@ static PassCtx make_ctx(const float *padded, int rx, int ry, int rz, const dsdf_
     c.Wb = W + 2 * DSDF_BORDER; c.Hb = H + 2 * DSDF_BORDER; c.nl = (uint32_t)(c.Wb * c.Hb * spp);
     c.row0 = 0; c.row1 = (int)c.Hb; c.film = nullptr; c.ws_bytes = 0;
     c.st = (hipStream_t)stream;
-    c.coef_early = false; c.coef_beside = false; c.coef_done_early = false;
+    c.coef_beside = false; c.coef_done_early = false;
     return c;
+}
+
+// the view arguments of views [v0, v0 + nv) of the call
+static void fill_views(const PassCtx &c, const dsdf_camera *cams, int v0, int nv, ViewBatch &VB) {
+    for (int i = 0; i < nv; ++i) {
+        const size_t v = (size_t)(v0 + i);
+        VB.v[i] = make_view_args(cams[v], c.W, c.H, c.spp, c.offsets ? c.offsets + v * c.nl * 2 : nullptr, c.seeds ? c.seeds[v] : 0u,
+                                 c.integrator, c.flags, c.pp, c.emitter_u ? c.emitter_u + v * c.nl * 2 : nullptr,
+                                 c.bsdf_u ? c.bsdf_u + v * c.nl * 2 : nullptr, c.lobe_u ? c.lobe_u + v * c.nl : nullptr);
+    }
 }
 
 // persistent workers of k_render_items: enough single-wave blocks to fill every wave slot of the device
@@ -1291,14 +1286,12 @@ static unsigned worker_blocks() {
     return n;
 }
 
-// Helper streams for the tail kernels.  A tail kernel is a few thousand waves that wait on the latency of their longest
-// rays; on a stream of its own it runs beside the next render kernel of the caller's stream.  Two high-priority streams per
-// (device, caller stream), created on first use; events come from a ring (an event may be re-recorded while an earlier
-// wait on it is still queued: the wait refers to the record that preceded it).  DSDF_TAIL_STREAMS=0 keeps everything on the
-// caller's stream, DSDF_GROUPS=n (1..4) sets the number of view groups.  Measured (profiles/r03a_tail_ab.md): a resident tail
-// kernel takes registers from the render kernel beside it (main kernels 6.0 -> 7.2-7.6 ms per 3-view group) and every group
-// boundary costs a list build + ramp, so ONE group is the default: the tail then runs behind its render kernel and
-// overlaps with whatever the caller has on its other streams (dsdf.render_step: the other pass).
+// Helper streams of the gradient sweep: k_backward_coef for the samples its render kernel queued itself runs on one of them,
+// beside the tail kernel on the caller's stream, and is joined back before the call returns.  Two high-priority streams per
+// (device, caller stream), created on first use (the coefficients run on the second); events come from a ring (an event may be
+// re-recorded while an earlier wait on it is still queued: the wait refers to the record that preceded it).  The tail kernel
+// itself stays on the caller's stream: view groups with their tail kernels on these streams, beside the next group's render
+// kernel, measured slower than one group (profiles/r03a_tail_ab.md) and were removed.
 struct TailStreams {
     int dev; hipStream_t owner; hipStream_t s[2];
 };
@@ -1313,46 +1306,16 @@ static int env_int(const char *name, int dflt) {
     return (v && *v) ? atoi(v) : dflt;
 }
 
-// DSDF_BWD_SPLIT=0: dsdf_grad_backward runs the fused k_backward instead of k_backward_coef (in dsdf_grad_sweep) + k_backward_apply
-static bool backward_split() { static const int v = env_int("DSDF_BWD_SPLIT", 1); return v != 0; }
-// DSDF_TAIL_QUEUES=xcd (default): tail sub-queue = (XCD of the producing worker, its ticket counter), drained by the blocks of that
-// XCD first; `item`: sub-queue = work-list index % 64 (round 3).  Measured (profiles/r04_tail_ab.md, profiles/r04_sq.json vs
-// r04_item_sq.json): with 4096 tail waves the per-XCD queues were SLOWER (a hard tile's long rays on an eighth of the waves: 4.4 ->
-// 6.1 ms), with ONE tail wave per SIMD -- what the longest chain wants anyway -- they win a little: k_tail_trace_plain L2 misses
-// 44 % -> 18 %, 2.6 -> 0.8 GB fetched, 3.1-3.5 -> 2.7-2.9 ms; step 41.0 -> 40.6 ms (three runs each).
-static int tail_per_xcd() { static const char *v = getenv("DSDF_TAIL_QUEUES"); return (v && !strcmp(v, "item")) ? 0 : 1; }
-// DSDF_FINE_HIT_PROOF=0: hit proof from the block maxima only (A/B)
-static bool fine_hit_proof() { static const int v = env_int("DSDF_FINE_HIT_PROOF", 1); return v != 0; }
-// DSDF_DEEP_SKIP=0: the samples of deep pixels are generated (and only their march is skipped)
-static bool deep_skip_enabled() { static const int v = env_int("DSDF_DEEP_SKIP", 1); return v != 0; }
-// DSDF_COEF_EARLY=1: k_backward_coef for the render kernel's own samples AHEAD of the tail kernel + a second launch for what the
-// tail appended.  Measured (profiles/r04_tail_ab.md): the early launch is starved by the primal workers just like the tail kernel
-// (15 ms resident), and the tail kernel then starts later: step 42.5 vs 40.8 ms.
-// DSDF_COEF_EARLY=2 (the default since round 6): the coefficients of the render kernel's own samples on a helper stream BESIDE the tail
-// kernel -- forked behind the render kernel and the snapshot of the queue lengths, in front of the tail kernel (the fork
-// event used to be recorded behind the tail kernel's launch, so "beside" ran after it and measured as no gain) -- and a second launch
-// for what the tail appended: step 36.08 -> 35.86 and 35.52 -> 35.23 ms on two boxes (profiles/r06_ab/coef_beside.jsonl).
-// DSDF_COEF_EARLY=0: one launch behind the tail kernel.
-static int coef_early_mode() { static const int v = env_int("DSDF_COEF_EARLY", 2); return v; }
-static int hit_proof_min_spp() { static const int v = env_int("DSDF_HIT_PROOF_MIN_SPP", 16); return v; }
-// DSDF_ENV_FILL=0: sdf_direct_reparam with a visible environment samples its far pixels (as until round 5; A/B)
-static bool env_fill_enabled() { static const int v = env_int("DSDF_ENV_FILL", 1); return v != 0; }
+// The two run-time switches; the tests use them to reach the reference path of a comparison.
+// DSDF_CELL_TABLE=0: the primal's shadow rays of sdf_direct_reparam read the grid, not the cell table (as large grids do anyway)
 static bool cell_table_enabled() { static const int v = env_int("DSDF_CELL_TABLE", 1); return v != 0; }
-// DSDF_DIRECT_WAVEFRONT: 0 = the fused workers of sdf_direct_reparam as until round 6, 1 = the primal as a wavefront, 2 = the gradient sweep too
-static int direct_wavefront_enabled() { static const int v = env_int("DSDF_DIRECT_WAVEFRONT", 2); return v; }
-static bool primal_handoff() { static const int v = env_int("DSDF_PRIMAL_HANDOFF", 1); return v != 0; }
-static int tail_streams_enabled() { static int v = env_int("DSDF_TAIL_STREAMS", 1); return v; }
-// blocks (4 waves) per sub-queue of a tail kernel: DSDF_TAIL_BLOCKS overrides the built-in value
-static unsigned tail_blocks() {
-    static int v = 0;
-    if (!v) { v = env_int("DSDF_TAIL_BLOCKS", DSDF_TAIL_BLOCKS_PER_SUBQ); v = v < 1 ? 1 : (v > 64 ? 64 : v); }
-    return (unsigned)v;
-}
-static int max_groups() {
-    static int v = 0;
-    if (!v) { v = env_int("DSDF_GROUPS", 1); v = v < 1 ? 1 : (v > DSDF_MAX_GROUPS ? DSDF_MAX_GROUPS : v); }
-    return v;
-}
+// DSDF_DIRECT_WAVEFRONT=0: sdf_direct_reparam's fused workers as until round 6, not the wavefront passes
+static bool direct_wavefront_enabled() { static const int v = env_int("DSDF_DIRECT_WAVEFRONT", 1); return v != 0; }
+
+// The hit proof serves the silhouette integrator, which consumes nothing but the hit flag of a sample.  It costs 0.4 + 0.6 ms per
+// 12-view call and saves marching in proportion to the samples per pixel: below this many samples -- of THIS call: in a shared
+// bracket the gradient sweep's -- it does not pay.
+static constexpr int HIT_PROOF_MIN_SPP = 16;
 
 static bool helper_streams(hipStream_t owner, hipStream_t out[2]) {
     int dev = 0;
@@ -1364,10 +1327,8 @@ static bool helper_streams(hipStream_t owner, hipStream_t out[2]) {
     t.dev = dev; t.owner = owner;
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);           // (hi = numerically lowest = highest priority)
-    static const int prio_mode = env_int("DSDF_TAIL_PRIORITY", 1);      // 1: highest (default), 0: default priority, -1: lowest
-    const int prio = prio_mode > 0 ? hi : (prio_mode < 0 ? lo : 0);
     for (int k = 0; k < 2; ++k)
-        if (hipStreamCreateWithPriority(&t.s[k], hipStreamNonBlocking, prio) != hipSuccess) return false;
+        if (hipStreamCreateWithPriority(&t.s[k], hipStreamNonBlocking, hi) != hipSuccess) return false;
     g_helpers.push_back(t);
     out[0] = t.s[0]; out[1] = t.s[1];
     return true;
@@ -1429,265 +1390,273 @@ static bool skip_share_matches(const SkipShare &h, const PassCtx &c, const dsdf_
            memcmp(&h.prm, c.prm, sizeof(dsdf_params)) == 0 && memcmp(h.cams, cams, (size_t)nv * sizeof(dsdf_camera)) == 0;
 }
 
+// Stage 1, the per-pixel proofs (dsdf_skip.h, dsdf_proof.h): the skip flags of the batch, computed into the workspace or the
+// caller's shared buffer, or read from that buffer when an earlier call of the bracket computed them.  skip = nullptr: no proof
+// (DSDF_NO_SKIP, or no level of the min-grid pays).
+static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera *cams, int nv, const ViewBatch &VB,
+                       const unsigned char *&skip) {
+    int rc;
+    hipStream_t st = c.st;
+    const size_t npix = c.Wb * c.Hb;
+    skip = nullptr;
+    float step = 0.f;
+    const int level = (c.flags & DSDF_NO_SKIP) ? -1 : skip_level(cams, nv, c.W, c.rx, c.ry, c.rz, step);
+    if (level < 0) return DSDF_OK;
+    SkipShare &sh = t_share;
+    const bool can_share = sh.buf && sh.ready && sh.bytes >= (size_t)nv * npix;
+    if (can_share && skip_share_matches(sh, c, cams, nv)) {
+        if (hipStreamWaitEvent(st, sh.ready, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipStreamWaitEvent(shared skip flags) failed");
+        skip = sh.buf;
+        return DSDF_OK;
+    }
+    unsigned char *dst = (can_share && !sh.valid) ? sh.buf : ws.skip;       // (a second, different batch keeps its own flags)
+    const bool want_hit = c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF) && c.spp >= HIT_PROOF_MIN_SPP;
+    const float hstep = want_hit ? hit_step(cams, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
+    const float fstep = want_hit ? hit_step_fine(cams, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
+    // the pixels neither proof settles are listed in the (not yet built) work-list area of this workspace for the second
+    // stage of the hit proof: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
+    uint32_t *und = fstep > 0.f ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
+    if (und && hipMemsetAsync(und, 0, sizeof(uint32_t), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(undecided list) failed");
+    // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try)
+    const float step0 = level > 0 ? skip_step(cams, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
+    hipLaunchKernelGGL(k_pixel_skip, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st,
+                       device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
+                       min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
+                       step0, step, hstep, und);
+    if (und)
+        hipLaunchKernelGGL(k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), dim3(256), 0, st,
+                           device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
+                           (const uint32_t *)und, (const uint32_t *)(und + DSDF_UNDECIDED_HDR), fstep);
+    if ((rc = check_launch("k_pixel_skip"))) return rc;
+    hipLaunchKernelGGL(k_skip_dilate, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st, VB, dst);
+    if ((rc = check_launch("k_skip_dilate"))) return rc;
+    if (dst == sh.buf) {
+        if (hipEventRecord(sh.ready, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipEventRecord(shared skip flags) failed");
+        sh.valid = true; sh.padded = c.padded; sh.rx = c.rx; sh.ry = c.ry; sh.rz = c.rz; sh.W = c.W; sh.H = c.H; sh.nv = nv;
+        sh.hit_proof = (int)want_hit;
+        sh.prm = *c.prm;
+        memcpy(sh.cams, cams, (size_t)nv * sizeof(dsdf_camera));
+    }
+    skip = dst;
+    return DSDF_OK;
+}
+
+// What the render stages of one batch share.
+struct Batch {
+    const ViewBatch &VB;
+    int nv;
+    GridView G;
+    ShadeArgs S;
+    Queue q;
+    float *film;
+    const unsigned char *skip;     // the proof's flags, or nullptr
+    unsigned long long *st64;      // per-call counters, or nullptr
+    bool deep_skip;                // silhouette primal: the samples of deep pixels are not generated (k_film_ones)
+    bool env_fill;                 // sdf_direct_reparam with a visible environment: far pixels are not sampled (k_film_env)
+};
+
+// Stage 2, the film values the proof settles: the film pixels that receive only hits of deep pixels get (1, 1), those that only
+// far pixels of sdf_direct_reparam reach get the environment's radiance.
+template <bool DIFF>
+static int prefill_film(const PassCtx &c, const Batch &b) {
+    int rc;
+    const dim3 grid((unsigned)((c.Wb * c.Hb + 255) / 256), b.nv), blk(256);
+    if (b.deep_skip) {
+        hipLaunchKernelGGL(k_film_ones, grid, blk, 0, c.st, b.VB, b.skip, b.film, c.row0, c.row1, b.st64);
+        if ((rc = check_launch("k_film_ones"))) return rc;
+    }
+    if (b.env_fill) {
+        hipLaunchKernelGGL(k_film_env, grid, blk, 0, c.st, b.VB, b.skip, b.film, c.row0, c.row1,
+                           DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY, b.S.env[0], b.S.env[1], b.S.env[2]);
+        if ((rc = check_launch("k_film_env"))) return rc;
+    }
+    return DSDF_OK;
+}
+
+// Stage 3 (spp a multiple of 64), the persistent workers over the compacted list of pixels that must be sampled: work list,
+// render kernel (k_render_items, or k_render_items_store for the wavefront primary rays), then the tail kernel that resumes the
+// rays its waves handed off -- in the gradient sweep with k_backward_coef for the render kernel's own samples beside it.
+template <bool DIFF>
+static int persistent_pass(PassCtx &c, const Workspace &ws, const Batch &b, bool wavefront) {
+    int rc;
+    hipStream_t st = c.st;
+    const int nv = b.nv;
+    // (sdf_direct_reparam with a visible environment and no proof: the background is not zero, every pixel is sampled)
+    // (for the silhouette primal also the pixels whose samples only reach film pixels of value 1: DSDF_PX_DEEP, k_skip_dilate)
+    // (sdf_direct_reparam with a visible environment: far pixels are skipped too since round 6 -- k_film_env gives the film
+    // pixels they alone would have reached the environment's radiance)
+    const unsigned far_bit = (c.direct && !b.S.hide_emitters && !b.env_fill) ? 0u : (DIFF ? DSDF_PX_FAR_G : (DSDF_PX_FAR | (b.deep_skip ? DSDF_PX_DEEP : 0u)));
+    if (hipMemsetAsync(ws.items, 0, (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR * sizeof(uint32_t), st) != hipSuccess)
+        return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(work list) failed");
+    // tile-major order: a tile = DSDF_ITEM_SEG chunks of 64 samples (16 x 16 pixels at 256 spp, 32 x 32 at 64 spp)
+    ItemOrder O;
+    {
+        unsigned tile_px = DSDF_ITEM_SEG / (unsigned)(c.spp / 64);
+        if (tile_px < 1) tile_px = 1;
+        int lg = 0;
+        while ((2u << lg) <= tile_px) ++lg;
+        O.tw_log2 = (lg + 1) / 2; O.th_log2 = lg / 2;
+        O.tiles_x = (unsigned)((c.Wb + (1u << O.tw_log2) - 1) >> O.tw_log2);
+        const unsigned tiles_y = (unsigned)((c.Hb + (1u << O.th_log2) - 1) >> O.th_log2);
+        O.per_view = (O.tiles_x * tiles_y) << (O.tw_log2 + O.th_log2);
+    }
+    if (DIFF && hipMemsetAsync(ws.count, 0, (size_t)nv * ws.nunits * sizeof(uint32_t), st) != hipSuccess)
+        return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(queue counts) failed");
+    const bool handoff = ws.tail != nullptr && (!c.direct || wavefront);
+    const size_t cnt_bytes = align_up((size_t)DSDF_MAX_GROUPS * DSDF_TAIL_SUBQ * DSDF_TAIL_CNT_STRIDE * sizeof(uint32_t), 256);
+    if (handoff && hipMemsetAsync(ws.tail, 0, cnt_bytes, st) != hipSuccess)
+        return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tail queue) failed");
+    uint32_t *hdr = ws.items;
+    uint32_t *list = ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR;
+    hipLaunchKernelGGL(k_build_items, dim3((unsigned)(((size_t)nv * O.per_view + DSDF_ITEM_REGION - 1) / DSDF_ITEM_REGION)), dim3(256), 0, st,
+                       b.VB, 0, nv, b.skip, far_bit, c.row0, c.row1, O, hdr, list);
+    if ((rc = check_launch("k_build_items"))) return rc;
+    TailQueue tq;
+    memset(&tq, 0, sizeof(tq));
+    if (handoff) {
+        // one queue over the ceil(nv / group_views) tail slices the batch's views take (carve, DSDF_MAX_GROUPS)
+        tq.cap_sub = ws.tail_cap_sub * (uint32_t)((nv + ws.group_views - 1) / ws.group_views);
+        tq.per_xcd = 1u;
+        tq.count = (uint32_t *)ws.tail;
+        tq.state = (float *)(ws.tail + cnt_bytes);
+    }
+    const GridView &G = b.G;
+    const ShadeArgs &S = b.S;
+    const Queue &q = b.q;
+    unsigned long long *st64 = b.st64;
+    // (the default fills every wave slot of the device, workers that find no slot start when others retire)
+    const dim3 grid(worker_blocks()), blk(64);
+    timing_mark(0, st);
+    if (wavefront) {
+        // the march of the primary rays into hit_t / the record rows (its tail kernel below); direct_wavefront does the rest
+        if (st64) hipLaunchKernelGGL((k_render_items_store<DIFF, true>), grid, blk, 0, st, G, c.pp, b.VB, q, st64, b.skip, S, tq, hdr, list, ws.hit_t);
+        else hipLaunchKernelGGL((k_render_items_store<DIFF, false>), grid, blk, 0, st, G, c.pp, b.VB, q, st64, b.skip, S, tq, hdr, list, ws.hit_t);
+    } else if (c.direct) {
+        if (st64) hipLaunchKernelGGL((k_render_items<DIFF, true, true>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
+        else hipLaunchKernelGGL((k_render_items<DIFF, true, false>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
+    } else {
+        if (st64) hipLaunchKernelGGL((k_render_items<DIFF, false, true>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
+        else hipLaunchKernelGGL((k_render_items<DIFF, false, false>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
+    }
+    if ((rc = check_launch("k_render_items"))) return rc;
+    timing_mark(1, st);
+    if (!handoff) return DSDF_OK;
+    bool coef_beside = false;
+    hipEvent_t coef_fork = nullptr;
+    hipStream_t hs[2] = {st, st};
+    if (DIFF && c.coef_beside && ws.count0 && helper_streams(st, hs)) {
+        // the queue lengths as the render kernel leaves them: the tail kernel appends behind them from now on
+        if (hipMemcpyAsync(ws.count0, ws.count, (size_t)nv * ws.nunits * sizeof(uint32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(DSDF_ERR_LAUNCH, "hipMemcpyAsync(queue lengths) failed");
+        coef_beside = true;
+        //  the fork event of the coefficient stream is recorded HERE -- behind the render kernel and the snapshot, in
+        // front of the tail kernel on this same stream: recorded after its launch the coefficients waited for the whole tail
+        // kernel and ran after it, not beside it
+        coef_fork = next_event();
+        if (!coef_fork || hipEventRecord(coef_fork, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
+    }
+    const dim3 tgrid(DSDF_TAIL_SUBQ * DSDF_TAIL_BLOCKS_PER_SUBQ), tblk(256);
+    unsigned long long *tst = st64 ? st64 : g_tail_stats;
+    if (DIFF && wavefront) hipLaunchKernelGGL((k_tail_trace_diff<true>), tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, q, (unsigned long long *)nullptr);
+    else if (DIFF) hipLaunchKernelGGL((k_tail_trace_diff<false>), tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, q, tst);
+    else hipLaunchKernelGGL(k_tail_trace_plain, tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, wavefront ? (unsigned long long *)nullptr : tst,
+                            wavefront ? ws.hit_t : (float *)nullptr);
+    if ((rc = check_launch("k_tail_trace"))) return rc;
+    if (coef_beside) {
+        // ... and the coefficients of the samples the render kernel queued itself on the helper stream, beside the tail kernel
+        // (it waits for the render kernel and the copy above); the caller's stream joins it
+        hipStream_t cs = hs[1];
+        if (hipStreamWaitEvent(cs, coef_fork, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
+        const dim3 cgrid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
+        hipLaunchKernelGGL(k_backward_coef, cgrid, dim3(64), 0, cs, G, c.pp, b.VB, q, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)ws.count0);
+        if ((rc = check_launch("k_backward_coef"))) return rc;
+        hipEvent_t join = next_event();
+        if (!join || hipEventRecord(join, cs) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream join failed");
+        c.coef_done_early = true;
+        if (hipStreamWaitEvent(st, join, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "tail stream join failed");
+    }
+    return DSDF_OK;
+}
+
+// Stage 4, the rest of sdf_direct_reparam's wavefront behind stage 3's primary rays: k_direct_items<0> queues the
+// shadow rays, the shadow stream marches them, k_direct_items<1> shades.
+template <bool DIFF>
+static int direct_wavefront(const PassCtx &c, const Workspace &ws, const Batch &b) {
+    int rc;
+    hipStream_t st = c.st;
+    uint32_t *hdr = ws.items;
+    const uint32_t *list = ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR;
+    const size_t scnt = align_up((size_t)DSDF_TAIL_SUBQ * DSDF_TAIL_CNT_STRIDE * sizeof(uint32_t), 256);
+    TailQueue sq;
+    sq.count = (uint32_t *)ws.shq; sq.state = (float *)(ws.shq + scnt); sq.cap_sub = ws.shq_cap_sub; sq.per_xcd = 1u;
+    const size_t tick_bytes = (size_t)16 * DSDF_TICKETS * sizeof(uint32_t);
+    const dim3 grid(worker_blocks()), blk(64), sgrid(DSDF_TAIL_SUBQ * DSDF_SHQ_BLOCKS_PER_SUBQ), sblk(256);
+    if (hipMemsetAsync(ws.shq, 0, scnt, st) != hipSuccess || hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess)
+        return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(shadow queue) failed");
+    hipLaunchKernelGGL((k_direct_items<0, DIFF>), grid, blk, 0, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q);
+    if ((rc = check_launch("k_direct_items<0>"))) return rc;
+    if (DIFF) {
+        hipLaunchKernelGGL(k_shadow_stream_diff, sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, b.q, b.st64);
+        if ((rc = check_launch("k_shadow_stream_diff"))) return rc;
+    } else {
+        // the cell table the shadow rays read, behind the carved workspace when the caller provided the room (dsdf_cell_table_size)
+        const size_t tb = cell_table_enabled() ? cell_table_bytes(c.rx, c.ry, c.rz) : 0;
+        const size_t toff = align_up(ws.bytes, 256);
+        float *table = (tb && c.ws_bytes >= toff + tb) ? (float *)((char *)ws.block + toff) : nullptr;
+        if (table) {
+            hipLaunchKernelGGL(k_cell_table, dim3(16384), dim3(256), 0, st, c.padded, c.rx + 2 * DSDF_APRON, c.ry + 2 * DSDF_APRON, c.rz + 2 * DSDF_APRON, table);
+            if ((rc = check_launch("k_cell_table"))) return rc;
+            hipLaunchKernelGGL((k_shadow_stream<true>), sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, ws.hit_t, b.st64, (const float *)table);
+        } else {
+            hipLaunchKernelGGL((k_shadow_stream<false>), sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, ws.hit_t, b.st64, (const float *)nullptr);
+        }
+        if ((rc = check_launch("k_shadow_stream"))) return rc;
+    }
+    if (hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tickets) failed");
+    hipLaunchKernelGGL((k_direct_items<1, DIFF>), grid, blk, 0, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q);
+    return check_launch("k_direct_items<1>");
+}
+
+// Stage 3 for the other sample counts: k_render_pass, one lane per sample.
+template <bool DIFF>
+static int lane_pass(const PassCtx &c, const Batch &b) {
+    LaneMap M;
+    size_t nunits;
+    pass_shape(c.W, c.H, c.spp, M.tile_w, M.tile_h, nunits);
+    M.n_lanes = c.nl; M.row0 = c.row0; M.row1 = c.row1; M.deep_mask = b.deep_skip ? DSDF_PX_DEEP : 0u; M.env_fill = b.env_fill ? 1 : 0;
+    const dim3 grid((unsigned)(nunits / 4), b.nv), blk(DSDF_BLOCK);
+    timing_mark(0, c.st);
+    if (c.direct) hipLaunchKernelGGL((k_render_pass<DIFF, true>), grid, blk, 0, c.st, b.G, c.pp, b.VB, b.film, b.q, b.st64, M, b.skip, b.S);
+    else hipLaunchKernelGGL((k_render_pass<DIFF, false>), grid, blk, 0, c.st, b.G, c.pp, b.VB, b.film, b.q, b.st64, M, b.skip, b.S);
+    int rc = check_launch("k_render_pass");
+    if (rc) return rc;
+    timing_mark(1, c.st);
+    return DSDF_OK;
+}
+
 template <bool DIFF>
 static int run_pass(PassCtx &c, const Workspace &ws, const dsdf_camera *cams, int v0, int nv, ViewBatch &VB, Queue q,
                     int64_t *stats) {
     int rc;
-    hipStream_t st = c.st;
-    for (int i = 0; i < nv; ++i)
-        VB.v[i] = make_view_args(cams[v0 + i], c.W, c.H, c.spp, c.offsets ? c.offsets + (size_t)(v0 + i) * c.nl * 2 : nullptr,
-                                 c.seeds ? c.seeds[v0 + i] : 0u, c.integrator, c.flags, c.pp,
-                                 c.emitter_u ? c.emitter_u + (size_t)(v0 + i) * c.nl * 2 : nullptr,
-                                 c.bsdf_u ? c.bsdf_u + (size_t)(v0 + i) * c.nl * 2 : nullptr,
-                                 c.lobe_u ? c.lobe_u + (size_t)(v0 + i) * c.nl : nullptr);
+    fill_views(c, cams, v0, nv, VB);
     const size_t nch = (size_t)film_channels(c.integrator), npix = c.Wb * c.Hb;
     float *film = c.film ? c.film + (size_t)v0 * npix * nch : ws.block;
-    if (!c.film && hipMemsetAsync(ws.block, 0, nv * npix * nch * sizeof(float), st) != hipSuccess)
+    if (!c.film && hipMemsetAsync(ws.block, 0, nv * npix * nch * sizeof(float), c.st) != hipSuccess)
         return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(film block) failed");
-    float step = 0.f;
-    const int level = (c.flags & DSDF_NO_SKIP) ? -1 : skip_level(cams + v0, nv, c.W, c.rx, c.ry, c.rz, step);
-    const unsigned char *skip = nullptr;
-    if (level >= 0) {
-        SkipShare &sh = t_share;
-        const bool can_share = sh.buf && sh.ready && sh.bytes >= (size_t)nv * npix;
-        if (can_share && skip_share_matches(sh, c, cams + v0, nv)) {
-            if (hipStreamWaitEvent(st, sh.ready, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipStreamWaitEvent(shared skip flags) failed");
-            skip = sh.buf;
-        } else {
-            unsigned char *dst = (can_share && !sh.valid) ? sh.buf : ws.skip;       // (a second, different batch keeps its own flags)
-            // (the hit proof serves the silhouette integrator, which consumes nothing but the hit flag of a sample)
-            // (the hit proof costs 0.4 + 0.6 ms per 12-view call and saves marching in proportion to the samples per pixel: below
-            // DSDF_HIT_PROOF_MIN_SPP samples -- of THIS call: in a shared bracket the gradient sweep's -- it does not pay)
-            const bool want_hit = c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF) && c.spp >= hit_proof_min_spp();
-            const float hstep = want_hit ? hit_step(cams + v0, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
-            const float fstep = (want_hit && fine_hit_proof()) ? hit_step_fine(cams + v0, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
-            // the pixels neither proof settles are listed in the (not yet built) work-list area of this workspace for the second
-            // stage of the hit proof: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
-            uint32_t *und = fstep > 0.f ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
-            if (und && hipMemsetAsync(und, 0, sizeof(uint32_t), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(undecided list) failed");
-            // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try)
-            const float step0 = level > 0 ? skip_step(cams + v0, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
-            hipLaunchKernelGGL(k_pixel_skip, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st,
-                               device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
-                               min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
-                               step0, step, hstep, und);
-            if (und)
-                hipLaunchKernelGGL(k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), dim3(256), 0, st,
-                                   device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
-                                   (const uint32_t *)und, (const uint32_t *)(und + DSDF_UNDECIDED_HDR), fstep);
-            if ((rc = check_launch("k_pixel_skip"))) return rc;
-            hipLaunchKernelGGL(k_skip_dilate, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st, VB, dst);
-            if ((rc = check_launch("k_skip_dilate"))) return rc;
-            if (dst == sh.buf) {
-                if (hipEventRecord(sh.ready, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipEventRecord(shared skip flags) failed");
-                sh.valid = true; sh.padded = c.padded; sh.rx = c.rx; sh.ry = c.ry; sh.rz = c.rz; sh.W = c.W; sh.H = c.H; sh.nv = nv;
-                sh.hit_proof = (int)want_hit;
-                sh.prm = *c.prm;
-                memcpy(sh.cams, cams + v0, (size_t)nv * sizeof(dsdf_camera));
-            }
-            skip = dst;
-        }
-    }
-    const GridView G = device_view(c.padded, c.rx, c.ry, c.rz, *c.prm);
+    const unsigned char *skip;
+    if ((rc = pixel_proof(c, ws, cams + v0, nv, VB, skip))) return rc;
     const ShadeArgs S = make_shade_args(c.shading, DIFF);
-    unsigned long long *st64 = (unsigned long long *)stats;
-    // hit proof, second half: the samples of deep pixels are not generated; the film pixels that receive hits only get (1, 1)
-    const bool deep_skip = !DIFF && skip && c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF) && deep_skip_enabled();
-    if (deep_skip) {
-        hipLaunchKernelGGL(k_film_ones, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st, VB, skip, film, c.row0, c.row1, st64);
-        if ((rc = check_launch("k_film_ones"))) return rc;
-    }
-    const bool env_fill = c.direct && skip && !S.hide_emitters && env_fill_enabled();
-    if (env_fill) {
-        hipLaunchKernelGGL(k_film_env, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st, VB, skip, film, c.row0, c.row1,
-                           DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY, S.env[0], S.env[1], S.env[2]);
-        if ((rc = check_launch("k_film_env"))) return rc;
-    }
+    const bool deep_skip = !DIFF && skip && c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF);
+    const bool env_fill = c.direct && skip && !S.hide_emitters;
+    const Batch b = {VB, nv, device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), S, q, film, skip, (unsigned long long *)stats, deep_skip, env_fill};
+    if ((rc = prefill_film<DIFF>(c, b))) return rc;
     if (c.spp % 64 == 0) {
-        // persistent workers over the compacted list of pixels that must be sampled
-        // (sdf_direct_reparam with a visible environment: the background is not zero, every pixel is sampled)
-        // (for the silhouette primal also the pixels whose samples only reach film pixels of value 1: DSDF_PX_DEEP, k_skip_dilate)
-        // (sdf_direct_reparam with a visible environment: far pixels are skipped too since round 6 -- k_film_env above gives the film
-        // pixels they alone would have reached the environment's radiance)
-        const unsigned far_bit = (c.direct && !S.hide_emitters && !env_fill) ? 0u : (DIFF ? DSDF_PX_FAR_G : (DSDF_PX_FAR | (deep_skip ? DSDF_PX_DEEP : 0u)));
-        if (hipMemsetAsync(ws.items, 0, (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR * sizeof(uint32_t), st) != hipSuccess)
-            return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(work list) failed");
-        // tile-major order: a tile = DSDF_ITEM_SEG chunks of 64 samples (16 x 16 pixels at 256 spp, 32 x 32 at 64 spp)
-        ItemOrder O;
-        {
-            unsigned tile_px = DSDF_ITEM_SEG / (unsigned)(c.spp / 64);
-            if (tile_px < 1) tile_px = 1;
-            int lg = 0;
-            while ((2u << lg) <= tile_px) ++lg;
-            O.tw_log2 = (lg + 1) / 2; O.th_log2 = lg / 2;
-            O.tiles_x = (unsigned)((c.Wb + (1u << O.tw_log2) - 1) >> O.tw_log2);
-            const unsigned tiles_y = (unsigned)((c.Hb + (1u << O.th_log2) - 1) >> O.th_log2);
-            O.per_view = (O.tiles_x * tiles_y) << (O.tw_log2 + O.th_log2);
-        }
-        if (DIFF && hipMemsetAsync(ws.count, 0, (size_t)nv * ws.nunits * sizeof(uint32_t), st) != hipSuccess)
-            return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(queue counts) failed");
-        // view groups: render kernel g on the caller's stream, tail kernel g on a helper stream beside render kernel g + 1
-        // sdf_direct_reparam's primal as a wavefront (DSDF_DIRECT_WAVEFRONT=0: the fused worker as before; use_mis keeps it)
-        const bool wavefront = c.direct && !S.use_mis && ws.shq != nullptr && (DIFF || ws.hit_t != nullptr) && direct_wavefront_enabled() &&
-                               (!DIFF || direct_wavefront_enabled() > 1) && max_groups() == 1;
-        const bool handoff = ws.tail != nullptr && (DIFF || primal_handoff()) && (!c.direct || wavefront);
-        const size_t cnt_bytes = align_up((size_t)DSDF_MAX_GROUPS * DSDF_TAIL_SUBQ * DSDF_TAIL_CNT_STRIDE * sizeof(uint32_t), 256);
-        const size_t grp_bytes = align_up((size_t)DSDF_TAIL_SUBQ * ws.tail_cap_sub * ws.tail_words * sizeof(float), 256);
-        if (handoff && hipMemsetAsync(ws.tail, 0, cnt_bytes, st) != hipSuccess)
-            return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tail queue) failed");
-        // a group = k x ws.group_views views (k = 1 unless DSDF_GROUPS asks for fewer, larger groups: the tail regions of k
-        // nominal groups are contiguous and serve as one with k times the sub-queue capacity)
-        int per = nv, kreg = 1;
-        if (handoff) {
-            const int gviews = (int)ws.group_views, want = (nv + max_groups() - 1) / max_groups();
-            kreg = (want + gviews - 1) / gviews;
-            per = kreg * gviews;
-        }
-        const int ngroups = (nv + per - 1) / per;
-        hipStream_t hs[2] = {st, st};
-        // (helper streams only pay with several view groups: with one group the tail kernel simply follows its render kernel on
-        // the caller's stream -- two-stream step 47.5 ms against 48.5 with the fork / join, profiles/r03a_tail_ab.md)
-        const bool forked = handoff && ngroups > 1 && tail_streams_enabled() && helper_streams(st, hs);
-        hipEvent_t joins[DSDF_MAX_BATCH];
-        int njoin = 0;
-        // (DSDF_PRIMAL_WORKERS / DSDF_SWEEP_WORKERS: persistent workers per SIMD of the two render kernels -- A/B switch; the
-        // default fills every wave slot of the device, workers that find no slot start when others retire)
-        static const int w_primal = env_int("DSDF_PRIMAL_WORKERS", 0), w_sweep = env_int("DSDF_SWEEP_WORKERS", 0);
-        const int w_mine = DIFF ? w_sweep : w_primal;
-        const dim3 grid(w_mine > 0 ? (worker_blocks() / 8u) * (unsigned)w_mine : worker_blocks()), blk(64);
-        for (int g = 0; g < ngroups; ++g) {
-            const int a = g * per, b = (a + per) < nv ? (a + per) : nv;
-            uint32_t *hdr = ws.items + (size_t)g * DSDF_ITEM_HDR;
-            uint32_t *list = ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR + (size_t)a * npix;
-            hipLaunchKernelGGL(k_build_items, dim3((unsigned)(((size_t)(b - a) * O.per_view + DSDF_ITEM_REGION - 1) / DSDF_ITEM_REGION)), dim3(256), 0, st,
-                               VB, a, b - a, skip, far_bit, c.row0, c.row1, O, hdr, list);
-            if ((rc = check_launch("k_build_items"))) return rc;
-            TailQueue tq;
-            memset(&tq, 0, sizeof(tq));
-            if (handoff) {
-                tq.cap_sub = ws.tail_cap_sub * (uint32_t)kreg;
-                tq.per_xcd = (uint32_t)tail_per_xcd();
-                tq.count = (uint32_t *)ws.tail + (size_t)g * DSDF_TAIL_SUBQ * DSDF_TAIL_CNT_STRIDE;
-                tq.state = (float *)(ws.tail + cnt_bytes + (size_t)g * kreg * grp_bytes);
-            }
-            if (g == 0) timing_mark(0, st);
-            if (wavefront) {
-                // the march of the primary rays into hit_t / the record rows (its tail kernel below), then the three wavefront passes
-                if (st64) hipLaunchKernelGGL((k_render_items_store<DIFF, true>), grid, blk, 0, st, G, c.pp, VB, q, st64, skip, S, tq, hdr, list, ws.hit_t);
-                else hipLaunchKernelGGL((k_render_items_store<DIFF, false>), grid, blk, 0, st, G, c.pp, VB, q, st64, skip, S, tq, hdr, list, ws.hit_t);
-            } else if (c.direct) {
-                if (st64) hipLaunchKernelGGL((k_render_items<DIFF, true, true>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, skip, S, tq, hdr, list);
-                else hipLaunchKernelGGL((k_render_items<DIFF, true, false>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, skip, S, tq, hdr, list);
-            } else {
-                if (st64) hipLaunchKernelGGL((k_render_items<DIFF, false, true>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, skip, S, tq, hdr, list);
-                else hipLaunchKernelGGL((k_render_items<DIFF, false, false>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, skip, S, tq, hdr, list);
-            }
-            if ((rc = check_launch("k_render_items"))) return rc;
-            if (g == ngroups - 1) timing_mark(1, st);
-            if (DIFF && handoff && c.coef_early && ngroups == 1 && ws.count0) {
-                // the coefficients of what the render kernel queued itself, ahead of the tail kernel (k_backward_coef's comment)
-                const dim3 cgrid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
-                hipLaunchKernelGGL(k_backward_coef, cgrid, dim3(64), 0, st, G, c.pp, VB, q, (const uint32_t *)nullptr, ws.count0, (const uint32_t *)nullptr);
-                if ((rc = check_launch("k_backward_coef"))) return rc;
-                c.coef_done_early = true;
-            }
-            bool coef_beside = false;
-            hipEvent_t coef_fork = nullptr;
-            hipStream_t chs[2] = {st, st};
-            if (DIFF && handoff && c.coef_beside && ngroups == 1 && ws.count0 && helper_streams(st, chs)) {
-                // the queue lengths as the render kernel leaves them: the tail kernel appends behind them from now on
-                if (hipMemcpyAsync(ws.count0, ws.count, (size_t)nv * ws.nunits * sizeof(uint32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                    return fail(DSDF_ERR_LAUNCH, "hipMemcpyAsync(queue lengths) failed");
-                coef_beside = true;
-                //  the fork event of the coefficient stream is recorded HERE -- behind the render kernel and the snapshot, in
-                // front of the tail kernel, which with one view group runs on this same stream: recorded after its launch the
-                // coefficients waited for the whole tail kernel and ran after it, not beside it
-                coef_fork = next_event();
-                if (!coef_fork || hipEventRecord(coef_fork, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
-            }
-            if (handoff) {
-                hipStream_t ts = st;
-                if (forked) {
-                    ts = hs[g & 1];
-                    hipEvent_t e = next_event();
-                    if (!e || hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(ts, e, 0) != hipSuccess)
-                        return fail(DSDF_ERR_LAUNCH, "tail stream fork failed");
-                }
-                const dim3 tgrid(DSDF_TAIL_SUBQ * tail_blocks()), tblk(256);
-                unsigned long long *tst = st64 ? st64 : g_tail_stats;
-                if (DIFF && wavefront) hipLaunchKernelGGL((k_tail_trace_diff<true>), tgrid, tblk, 0, ts, G, c.pp, VB, film, tq, q, (unsigned long long *)nullptr);
-                else if (DIFF) hipLaunchKernelGGL((k_tail_trace_diff<false>), tgrid, tblk, 0, ts, G, c.pp, VB, film, tq, q, tst);
-                else hipLaunchKernelGGL(k_tail_trace_plain, tgrid, tblk, 0, ts, G, c.pp, VB, film, tq, wavefront ? (unsigned long long *)nullptr : tst,
-                                        wavefront ? ws.hit_t : (float *)nullptr);
-                if ((rc = check_launch("k_tail_trace"))) return rc;
-                if (forked) {
-                    hipEvent_t e = next_event();
-                    if (!e || hipEventRecord(e, ts) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "tail stream join failed");
-                    joins[njoin++] = e;
-                }
-                if (coef_beside) {
-                    // ... and the coefficients of the samples the render kernel queued itself on the OTHER helper stream, beside the tail
-                    // kernel (it waits for the render kernel and the copy above)
-                    hipStream_t cs = chs[1];
-                    if (hipStreamWaitEvent(cs, coef_fork, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
-                    const dim3 cgrid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
-                    hipLaunchKernelGGL(k_backward_coef, cgrid, dim3(64), 0, cs, G, c.pp, VB, q, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)ws.count0);
-                    if ((rc = check_launch("k_backward_coef"))) return rc;
-                    hipEvent_t e2 = next_event();
-                    if (!e2 || hipEventRecord(e2, cs) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream join failed");
-                    joins[njoin++] = e2;
-                    c.coef_done_early = true;
-                }
-            }
-        }
-        for (int k = 0; k < njoin; ++k)
-            if (hipStreamWaitEvent(st, joins[k], 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "tail stream join failed");
-        if (wavefront) {
-            // (one view group: the list of group 0 is the list of the launch)
-            uint32_t *hdr = ws.items;
-            const uint32_t *list = ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR;
-            const size_t scnt = align_up((size_t)DSDF_TAIL_SUBQ * DSDF_TAIL_CNT_STRIDE * sizeof(uint32_t), 256);
-            TailQueue sq;
-            sq.count = (uint32_t *)ws.shq; sq.state = (float *)(ws.shq + scnt); sq.cap_sub = ws.shq_cap_sub; sq.per_xcd = 1u;
-            const size_t tick_bytes = (size_t)16 * DSDF_TICKETS * sizeof(uint32_t);
-            if (hipMemsetAsync(ws.shq, 0, scnt, st) != hipSuccess || hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess)
-                return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(shadow queue) failed");
-            hipLaunchKernelGGL((k_direct_items<0, DIFF>), grid, blk, 0, st, G, c.pp, VB, film, skip, S, sq, hdr, list, ws.hit_t, q);
-            if ((rc = check_launch("k_direct_items<0>"))) return rc;
-            if (DIFF) {
-                hipLaunchKernelGGL(k_shadow_stream_diff, dim3(DSDF_TAIL_SUBQ * DSDF_SHQ_BLOCKS_PER_SUBQ), dim3(256), 0, st, G, c.pp, VB, sq, q, st64);
-                if ((rc = check_launch("k_shadow_stream_diff"))) return rc;
-            } else {
-            // the cell table the shadow rays read, behind the carved workspace when the caller provided the room (dsdf_cell_table_size)
-            const size_t tb = cell_table_enabled() ? cell_table_bytes(c.rx, c.ry, c.rz) : 0;
-            const size_t toff = align_up(ws.bytes, 256);
-            float *table = (tb && c.ws_bytes >= toff + tb) ? (float *)((char *)ws.block + toff) : nullptr;
-            if (table) {
-                hipLaunchKernelGGL(k_cell_table, dim3(16384), dim3(256), 0, st, c.padded, c.rx + 2 * DSDF_APRON, c.ry + 2 * DSDF_APRON, c.rz + 2 * DSDF_APRON, table);
-                if ((rc = check_launch("k_cell_table"))) return rc;
-                hipLaunchKernelGGL((k_shadow_stream<true>), dim3(DSDF_TAIL_SUBQ * DSDF_SHQ_BLOCKS_PER_SUBQ), dim3(256), 0, st, G, c.pp, VB, sq, ws.hit_t, st64, (const float *)table);
-            } else {
-                hipLaunchKernelGGL((k_shadow_stream<false>), dim3(DSDF_TAIL_SUBQ * DSDF_SHQ_BLOCKS_PER_SUBQ), dim3(256), 0, st, G, c.pp, VB, sq, ws.hit_t, st64, (const float *)nullptr);
-            }
-            if ((rc = check_launch("k_shadow_stream"))) return rc;
-            }
-            if (hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tickets) failed");
-            hipLaunchKernelGGL((k_direct_items<1, DIFF>), grid, blk, 0, st, G, c.pp, VB, film, skip, S, sq, hdr, list, ws.hit_t, q);
-            if ((rc = check_launch("k_direct_items<1>"))) return rc;
-        }
-    } else {
-        LaneMap M;
-        size_t nunits;
-        pass_shape(c.W, c.H, c.spp, M.tile_w, M.tile_h, nunits);
-        M.n_lanes = c.nl; M.row0 = c.row0; M.row1 = c.row1; M.deep_mask = deep_skip ? DSDF_PX_DEEP : 0u; M.env_fill = env_fill ? 1 : 0;
-        const dim3 grid((unsigned)(nunits / 4), nv), blk(DSDF_BLOCK);
-        timing_mark(0, st);
-        if (c.direct) hipLaunchKernelGGL((k_render_pass<DIFF, true>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, M, skip, S);
-        else hipLaunchKernelGGL((k_render_pass<DIFF, false>), grid, blk, 0, st, G, c.pp, VB, film, q, st64, M, skip, S);
-        if ((rc = check_launch("k_render_pass"))) return rc;
-        timing_mark(1, st);
+        // sdf_direct_reparam's primary rays as a wavefront (DSDF_DIRECT_WAVEFRONT=0: the fused worker; use_mis keeps it)
+        const bool wavefront = c.direct && !S.use_mis && ws.shq != nullptr && (DIFF || ws.hit_t != nullptr) && direct_wavefront_enabled();
+        if ((rc = persistent_pass<DIFF>(c, ws, b, wavefront))) return rc;
+        return wavefront ? direct_wavefront<DIFF>(c, ws, b) : DSDF_OK;
     }
-    return DSDF_OK;
+    return lane_pass<DIFF>(c, b);
 }
 
 static Queue make_queue(const Workspace &ws, bool direct) {
@@ -1915,14 +1884,12 @@ int dsdf_grad_sweep(const float *padded, int rx, int ry, int rz, const dsdf_para
     const Workspace ws = carve(workspace, width, height, spp, n_views, integrator, true);
     ViewBatch VB;
     const Queue q = make_queue(ws, c.direct);
-    c.coef_early = q.coef && backward_split() && coef_early_mode() == 1;
-    c.coef_beside = q.coef && backward_split() && coef_early_mode() == 2;
-    int rc2 = run_pass<true>(c, ws, cams, 0, n_views, VB, q, nullptr);
-    if (rc2) return rc2;
-    if (q.coef && backward_split()) {
+    c.coef_beside = q.coef != nullptr;
+    if ((rc = run_pass<true>(c, ws, cams, 0, n_views, VB, q, nullptr))) return rc;
+    if (q.coef) {
         // the image-independent half of the adjoint of the queued samples, now: the caller has the primal pass to run (or
         // running on another stream) before it can hand over the image gradient.  (If run_pass already did the render kernel's
-        // own samples, only what the tail kernel appended is left.)
+        // own samples beside the tail kernel, only what the tail kernel appended is left.)
         const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, n_views);
         hipLaunchKernelGGL(k_backward_coef, grid, dim3(64), 0, c.st, device_view(padded, rx, ry, rz, *prm), c.pp, VB, q,
                            (const uint32_t *)(c.coef_done_early ? ws.count0 : nullptr), (uint32_t *)nullptr, (const uint32_t *)nullptr);
@@ -1947,10 +1914,7 @@ int dsdf_grad_backward(const float *padded, int rx, int ry, int rz, const dsdf_p
     const Workspace ws = carve(workspace, width, height, spp, n_views, integrator, true);
     const Queue q = make_queue(ws, c.direct);
     ViewBatch VB;
-    for (int i = 0; i < n_views; ++i)
-        VB.v[i] = make_view_args(cams[i], width, height, spp, offsets ? offsets + (size_t)i * c.nl * 2 : nullptr, seeds ? seeds[i] : 0u,
-                                 integrator, flags, c.pp, c.emitter_u ? c.emitter_u + (size_t)i * c.nl * 2 : nullptr,
-                                 c.bsdf_u ? c.bsdf_u + (size_t)i * c.nl * 2 : nullptr, c.lobe_u ? c.lobe_u + (size_t)i * c.nl : nullptr);
+    fill_views(c, cams, 0, n_views, VB);
     const dim3 adj_grid((unsigned)((c.Wb * c.Hb + 255) / 256), n_views);
     if (c.direct) hipLaunchKernelGGL(k_develop_adjoint_rgb, adj_grid, dim3(256), 0, st, film_total, grad_image, width, height, ws.block_adj);
     else hipLaunchKernelGGL(k_develop_adjoint, adj_grid, dim3(256), 0, st, film_total, grad_image, width, height, ws.block_adj);
@@ -1959,7 +1923,7 @@ int dsdf_grad_backward(const float *padded, int rx, int ry, int rz, const dsdf_p
     const ShadeArgs S = make_shade_args(shading, true);
     const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, n_views);
     if (c.direct) hipLaunchKernelGGL(k_backward<true>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, (unsigned long long *)nullptr, S);
-    else if (grad_p || !q.coef || !backward_split()) hipLaunchKernelGGL(k_backward<false>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, (unsigned long long *)nullptr, S);
+    else if (grad_p || !q.coef) hipLaunchKernelGGL(k_backward<false>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, (unsigned long long *)nullptr, S);
     else hipLaunchKernelGGL(k_backward_apply, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid);     // (coefficients: dsdf_grad_sweep)
     return check_launch("k_backward");
 }

@@ -20,8 +20,8 @@
 // tiles, and a tail block drains the queues of the XCD it runs on first (then helps the others: every queue is drained
 // whatever the block -> XCD mapping is): 18 % misses, 0.8 GB, and -- with one wave per SIMD -- 0.4 ms off the step
 // (profiles/r04_tail_ab.md; with 4096 tail waves the same mapping was slower: a hard tile's rays land on an eighth of the waves).
-// (The host side can still cut a launch into view groups with the tail kernel of group g on a helper stream beside the render
-// kernel of group g + 1 -- DSDF_GROUPS; measured slower than one group, profiles/r03a_tail_ab.md, r04_tail_ab.md.)
+// (View groups -- the tail kernel of group g on a helper stream beside the render kernel of group g + 1 -- measured slower
+// than one group and were removed, profiles/r03a_tail_ab.md, r04_tail_ab.md.)
 #pragma once
 
 #ifndef DSDF_TAIL_HANDOFF
@@ -48,35 +48,8 @@
 #ifndef DSDF_TAIL_PRIO
 #define DSDF_TAIL_PRIO 3
 #endif
-#ifndef DSDF_TAIL_DIFF_REUSE
-#define DSDF_TAIL_DIFF_REUSE 1      /* the gradient sweep's tail rays keep the 64 taps of their cell in registers (ReuseFetch, like the primal tail):
-                                       alone on the chip that bought nothing (round 2: 4.5 -> 4.6 ms), but in the two-stream step the kernel crawls
-                                       beside the primal workers for 15 ms and every gather it does NOT issue is a loaded-L2 round trip off the
-                                       chain of its longest rays: step 40.6 -> 38.4 ms (profiles/r05_ab.md) */
-#endif
-#ifndef DSDF_TAIL_BATCH
-#define DSDF_TAIL_BATCH 1           /* a finished ray's sample (film splat, shading lookup, backward-queue entry with its returning atomic) is completed
-                                       when the wave refills -- with the >= DSDF_TAIL_REFILL others that finished since -- instead of inside the march
-                                       step in which the ray ended: a tail wave finishes 0.8 rays per lock-step iteration, so nearly every
-                                       iteration of its longest ray's chain carried a completion.  Same samples, same values (the order of the
-                                       film's float adds moves).  Primal call 19.96 -> 19.49 ms, gradient call 25.64 -> 24.87, step 39.53 -> 38.69 ms
-                                       (two runs each in one call, profiles/r05_ab.md r05u) */
-#endif
-#ifndef DSDF_TAIL_VIEWS_IN_LDS
-#define DSDF_TAIL_VIEWS_IN_LDS 1
-#endif
-#ifndef DSDF_TAIL_DEFER
-#define DSDF_TAIL_DEFER 0           /* (measured, r05u: NOT a gain -- primal call +0.4 ms alone, +0.1 ... +0.3 ms on top of DSDF_TAIL_BATCH; the rays that
-                                       sit an iteration out cost 12 % more lock-step iterations and the wait was not the gather's)
-                                       bit 0: k_tail_trace_plain, bit 1: k_tail_trace_diff overlap the gathers of the rays that change cell with the step of the others */
-#endif
 #ifndef DSDF_TAIL_CNT_STRIDE
 #define DSDF_TAIL_CNT_STRIDE 32     /* uint32 words between the {queued, claimed} pairs of two sub-queues: a 128-byte line each (2 = packed, as before round 5) */
-#endif
-#ifndef DSDF_TAIL_SCAN
-#define DSDF_TAIL_SCAN 1            /* a tail wave that has drained a sub-queue looks at ALL 64 {queued, claimed} pairs in one round trip and goes to the
-                                       next one with unclaimed entries (0: it visits them one by one, with a claim that comes back empty for every
-                                       sub-queue another wave has drained already) */
 #endif
 #define DSDF_TAIL_SUBQ 64           /* sub-queues per launch: 8 per XCD (one per ticket counter of the render kernel's XCD share) */
 #ifndef DSDF_TAIL_REFILL
@@ -263,7 +236,6 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
     const float *ent = nullptr;
     // opens the next sub-queue with unclaimed entries; false when there is none left
     auto open_next = [&]() {
-#if DSDF_TAIL_SCAN
         // lane k looks at the sub-queue this wave would visit k-th: one round trip for all of them (the claimed counters move under
         // device-scope atomics of other waves: an atomic load, not a cached one)
         const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
@@ -280,22 +252,8 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
         ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_TAIL_WORDS;
         total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
         return true;
-#else
-        while (hop < DSDF_TAIL_SUBQ) {
-            const uint32_t sub = tail_hop(first, hop++, tq.per_xcd);
-            cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-            ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_TAIL_WORDS;
-            total = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt[0]);
-            if (total != 0) return true;
-        }
-        return false;
-#endif
     };
-#if DSDF_TAIL_VIEWS_IN_LDS
     DSDF_TAIL_VIEWS_LDS(VB, views);
-#else
-    const ViewArgs *views = VB.v;
-#endif
     const unsigned long long t_start = stats ? wall_clock64() : 0ull, c_start = stats ? (unsigned long long)clock64() : 0ull;
     unsigned long long c_refill = 0, c_sec[5] = {0, 0, 0, 0, 0};
     if (!open_next()) return;
@@ -305,9 +263,7 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
     uint32_t sample = 0, view = 0;
     bool exhausted = false;
     int n_steps = 0, n_wsteps = 0, n_rays = 0, n_hits = 0, n_need = 0;
-#if DSDF_TAIL_DIFF_REUSE
-    ReuseFetch RF;
-#endif
+    ReuseFetch RF;                                                      // (the taps of the cell in registers, as in the primal tail)
 
     // the sample of this lane is complete: what the render pass does after its loop
     auto complete = [&]() {
@@ -341,14 +297,14 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
         }
     };
 
-    bool done = false;                                                  // (DSDF_TAIL_BATCH) marched to the end, sample not completed yet
+    // a finished ray's sample is completed at the wave's next refill, together with the others that finished since: nearly every
+    // iteration of the longest ray's chain would otherwise carry a completion
+    bool done = false;                                                  // marched to the end, sample not completed yet
     while (true) {
         const uint64_t idle = __ballot(!m.active);
         if (!exhausted && __popcll(idle) >= DSDF_TAIL_REFILL) {
             const unsigned long long c_in = stats ? (unsigned long long)clock64() : 0ull;
-#if DSDF_TAIL_BATCH
             if (done) { complete(); done = false; }
-#endif
             const unsigned long long c_a = stats ? (unsigned long long)clock64() : 0ull;
             bool drained = false;
             const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
@@ -366,9 +322,7 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
                 m.wdsum = mk(e[16], e[17], e[18]); m.ews_d = mk(e[19], e[20], e[21]);
                 m.i = __float_as_int(e[22]);
                 ++n_rays;
-#if DSDF_TAIL_DIFF_REUSE
                 RF.valid = false;
-#endif
             }
             if (stats) {
                 const unsigned long long c_e = (unsigned long long)clock64();
@@ -381,73 +335,15 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
             if (exhausted) break;
             continue;
         }
-#if DSDF_COOP_TAIL & 2
-        // the queues are drained and a few rays are left in this wave: 16 lanes per ray (dsdf_coop.h)
-        if (exhausted && __popcll(am) <= DSDF_COOP_RAYS) {
-            const bool mine = m.active;
-            const int i0 = m.i;
-            coop_finish_diff(G, P, m, am, lane_id());
-            if (mine) { n_steps += m.i - i0; done = true; }
-            break;
-        }
-#endif
         ++n_wsteps;
-#if (DSDF_TAIL_DEFER & 2) && DSDF_TAIL_DIFF_REUSE
-        if (m.active) {                                                 // (as in k_tail_trace_plain below)
-            const V3 x = fma3(m.t, m.d, m.o);
-            const CubicCell c = cubic_cell(G, x);
-            const bool load = !RF.valid || c.base != RF.base;
-            float stage[64];
-            if (load) {
-                const GlobalRows rows = global_rows(G, c);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        v2f lo, hi;
-                        rows.get(k, j, lo, hi);
-                        float *r = stage + (k * 4 + j) * 4;
-                        r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
-                    }
-            }
-            if (!opaque((int)load)) {
-                RegRows rr;
-                rr.t = RF.taps;
-                float v; V3 g; float H[6];
-                eval_cubic_rows<2>(G, c, rr, v, g, H);
-                diff_march_step(P, m, x, v, g, H);
-                ++n_steps;
-#if DSDF_TAIL_BATCH
-                done = !m.active;
-#else
-                if (!m.active) complete();
-#endif
-            }
-            if (opaque((int)load)) {
-#pragma unroll
-                for (int q = 0; q < 64; ++q) RF.taps[q] = stage[q];
-                RF.base = c.base;
-                RF.valid = true;
-            }
-        }
-#else
         if (m.active) {
             V3 x = fma3(m.t, m.d, m.o);
             float v; V3 g; float H[6];
-#if DSDF_TAIL_DIFF_REUSE
             RF.template eval<2>(G, x, true, v, g, H);
-#else
-            eval_cubic<2>(G, x, v, g, H);
-#endif
             diff_march_step(P, m, x, v, g, H);
             ++n_steps;
-#if DSDF_TAIL_BATCH
             done = !m.active;
-#else
-            if (!m.active) complete();
-#endif
         }
-#endif
     }
     if (done) complete();
     if (stats) {
@@ -474,7 +370,6 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
     uint32_t *cnt = nullptr;
     const float *ent = nullptr;
     auto open_next = [&]() {
-#if DSDF_TAIL_SCAN
         // lane k looks at the sub-queue this wave would visit k-th: one round trip for all of them (the claimed counters move under
         // device-scope atomics of other waves: an atomic load, not a cached one)
         const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
@@ -491,22 +386,8 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
         ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_PTAIL_WORDS;
         total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
         return true;
-#else
-        while (hop < DSDF_TAIL_SUBQ) {
-            const uint32_t sub = tail_hop(first, hop++, tq.per_xcd);
-            cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-            ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_PTAIL_WORDS;
-            total = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt[0]);
-            if (total != 0) return true;
-        }
-        return false;
-#endif
     };
-#if DSDF_TAIL_VIEWS_IN_LDS
     DSDF_TAIL_VIEWS_LDS(VB, views);
-#else
-    const ViewArgs *views = VB.v;
-#endif
     const unsigned long long t_start = stats ? wall_clock64() : 0ull, c_start = stats ? (unsigned long long)clock64() : 0ull;
     unsigned long long c_refill = 0, c_sec[5] = {0, 0, 0, 0, 0};
     if (!open_next()) return;
@@ -537,14 +418,12 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
         ++n_hits; n_ref += nref;
     };
 
-    bool done = false;                                                  // (DSDF_TAIL_BATCH) a hit whose sample is not completed yet
+    bool done = false;                                                  // a hit whose sample is not completed yet (as in k_tail_trace_diff)
     while (true) {
         const uint64_t idle = __ballot(!m.active);
         if (!exhausted && __popcll(idle) >= DSDF_TAIL_REFILL) {
             const unsigned long long c_in = stats ? (unsigned long long)clock64() : 0ull;
-#if DSDF_TAIL_BATCH
             if (done) { complete(); done = false; }
-#endif
             const unsigned long long c_a = stats ? (unsigned long long)clock64() : 0ull;
             bool drained = false;
             const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
@@ -571,68 +450,14 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
             if (exhausted) break;
             continue;
         }
-#if DSDF_COOP_TAIL & 1
-        if (exhausted && __popcll(am) <= DSDF_COOP_RAYS) {              // (as in k_tail_trace_diff)
-            const bool mine = m.active;
-            coop_finish_plain(G, m, am, lane_id(), n_steps);
-            if (mine && m.its_t < INFINITY) done = true;
-            break;
-        }
-#endif
         ++n_wsteps;
-#if DSDF_TAIL_DEFER & 1
-        // A ray that enters another cell ISSUES the gather of its 16 rows in this iteration and sits it out; the rays that stay in
-        // their cell take their step meanwhile, and the rows are moved to the lane's tap registers after that -- the wave waits for
-        // what is left of the memory round trip after a step's arithmetic instead of for all of it before.
-        if (m.active) {
-            const CubicCell c = cubic_cell(G, fma3(m.t, m.d, m.o));
-            const bool load = !F.valid || c.base != F.base;
-            float stage[64];
-            if (load) {
-                const GlobalRows rows = global_rows(G, c);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        v2f lo, hi;
-                        rows.get(k, j, lo, hi);
-                        float *r = stage + (k * 4 + j) * 4;
-                        r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
-                    }
-            }
-            if (!opaque((int)load)) {                                   // (opaque: keeps the program order issue -> step -> move)
-                RegRows rr;
-                rr.t = F.taps;
-                float v = 0.f; V3 gd; float Hd[6];
-                eval_cubic_rows<0>(G, c, rr, v, gd, Hd);
-                plain_march_step(m, v);
-                ++n_steps;
-#if DSDF_TAIL_BATCH
-                done = !m.active && m.its_t < INFINITY;
-#else
-                if (!m.active && m.its_t < INFINITY) complete();
-#endif
-            }
-            if (opaque((int)load)) {
-#pragma unroll
-                for (int q = 0; q < 64; ++q) F.taps[q] = stage[q];
-                F.base = c.base;
-                F.valid = true;
-            }
-        }
-#else
         if (m.active) {
             float v = 0.f; V3 gd; float Hd[6];
             F.template eval<0>(G, fma3(m.t, m.d, m.o), true, v, gd, Hd);
             plain_march_step(m, v);
             ++n_steps;
-#if DSDF_TAIL_BATCH
             done = !m.active && m.its_t < INFINITY;
-#else
-            if (!m.active && m.its_t < INFINITY) complete();
-#endif
         }
-#endif
     }
     if (done) complete();
     if (stats) {
@@ -728,9 +553,6 @@ __global__ void k_cell_table(const float *__restrict__ padded, int sx, int sy, i
 #ifndef DSDF_SHQ_REFILL
 #define DSDF_SHQ_REFILL 24
 #endif
-#ifndef DSDF_SHQ_DEFER
-#define DSDF_SHQ_DEFER 0
-#endif
 #ifndef DSDF_SHQ_BLOCKS_PER_SUBQ
 #define DSDF_SHQ_BLOCKS_PER_SUBQ 8      /* x 4 waves x 64 sub-queues = 2048 waves: 2 per SIMD at 186 VGPRs (a throughput kernel, unlike the tails) */
 #endif
@@ -795,45 +617,6 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
             continue;
         }
         ++n_wsteps;
-#if DSDF_SHQ_DEFER
-        static_assert(!TABLE, "the deferred variant reads the row-block copy");
-        // a ray that enters another cell ISSUES the gather of its 16 rows and sits this iteration out; the rays that stay in their cell
-        // step meanwhile, the rows are moved to the lane's tap registers after that: the wave waits for what is left of the memory
-        // round trip after a step's arithmetic.  (With ~50 marching rays per wave some ray changes its cell in nearly every iteration:
-        // without this every iteration is a round trip.)
-        if (m.active) {
-            const CubicCell c = cubic_cell(G, fma3(m.t, m.d, m.o));
-            const bool load = !F.valid || c.base != F.base;
-            float stage[64];
-            if (load) {
-                const GlobalRows rows = global_rows(G, c);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        v2f lo, hi;
-                        rows.get(k, j, lo, hi);
-                        float *r = stage + (k * 4 + j) * 4;
-                        r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
-                    }
-            }
-            if (!opaque((int)load)) {
-                RegRows rr;
-                rr.t = F.taps;
-                float v = 0.f; V3 gd; float Hd[6];
-                eval_cubic_rows<0>(G, c, rr, v, gd, Hd);
-                plain_march_step(m, v);
-                ++n_steps;
-                if (!m.active && m.its_t < INFINITY) hit_t[slot] = -my_t;   // occluded
-            }
-            if (opaque((int)load)) {
-#pragma unroll
-                for (int q = 0; q < 64; ++q) F.taps[q] = stage[q];
-                F.base = c.base;
-                F.valid = true;
-            }
-        }
-#else
         if (m.active) {
             float v = 0.f; V3 gd; float Hd[6];
             F.template eval<0>(G, fma3(m.t, m.d, m.o), true, v, gd, Hd);
@@ -841,7 +624,6 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
             ++n_steps;
             if (!m.active && m.its_t < INFINITY) hit_t[slot] = -my_t;       // occluded
         }
-#endif
     }
     if (stats) {
         const int ls = wave_sum_i32(n_steps), r = wave_sum_i32(n_rays);

@@ -3,13 +3,6 @@
 #pragma once
 
 // ------------------------------------------------------------------ wave helpers
-// An opaque copy of a lane-constant value: what is derived from it cannot be hoisted out of the enclosing loops (the
-// persistent render kernel keeps ~40 such values live across its march loops otherwise and spills).
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 __device__ __forceinline__ int lane_id() {
     return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }

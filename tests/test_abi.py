@@ -120,3 +120,14 @@ def test_build_staleness_covers_every_source(tmp_path):
         assert not g._newer(str(tgt), srcs), s
         os.utime(s, (old, old))
     assert not g._newer(str(tmp_path / 'missing.so'), srcs)
+
+
+def test_runtime_switches_of_the_library():
+    """The library reads exactly the two run-time switches INTEGRATION.md lists (the tests use them to reach the reference path of a
+    comparison); the A/B switches of earlier rounds were retired with the paths they selected."""
+    csrc = os.path.join(ROOT, 'differentiable-sdf-rendering_amd', 'csrc')
+    names = set()
+    for f in os.listdir(csrc):
+        src = open(os.path.join(csrc, f)).read()
+        names |= set(re.findall(r'\b(?:getenv|env_int)\s*\(\s*"([^"]+)"', src))
+    assert names == {'DSDF_DIRECT_WAVEFRONT', 'DSDF_CELL_TABLE'}

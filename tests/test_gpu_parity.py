@@ -454,7 +454,7 @@ def test_hit_proof_is_exact(dsdf, spp):
     assert d['all']['hits'] == d['empty']['hits'] == d['none']['hits'] > 0
     assert rel_l2(a.cpu(), b.cpu()) < 1e-6 and rel_l2(a.cpu(), c.cpu()) < 1e-6
     if spp < 16:
-        # below DSDF_HIT_PROOF_MIN_SPP (16) samples per pixel the proof costs more than the marching it saves: not computed
+        # below 16 samples per pixel (HIT_PROOF_MIN_SPP, csrc/dsdf_kernels.hip) the proof costs more than the marching it saves: not computed
         assert d['all']['lanes'] == d['empty']['lanes'] and d['all']['all_steps'] == d['empty']['all_steps']
     else:
         # (deep pixels -- whole +-4 neighbourhood proven -- are not even sampled: fewer generated lanes, their samples counted as hits)

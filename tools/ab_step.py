@@ -1,4 +1,4 @@
-"""A/B of one build / one setting (DSDF_LIB_PATH, DSDF_GROUPS, DSDF_TAIL_STREAMS ...) on the bench workload (256^3, 12 views x
+"""A/B of one build / one setting (DSDF_LIB_PATH, DSDF_SHARE_SKIP, DSDF_CELL_TABLE ...) on the bench workload (256^3, 12 views x
 512^2, silhouette, 256 / 64 spp): launch times of the primal render, the gradient pass and the two-stream step of bench.py,
 plus checksums of the image and of dL/dsdf (two settings that compute the same samples agree to the order of the float
 atomics).  Prints one line `AB {json}`.  `--shade` adds the simple-shading integrator, `--low` the 4/1-spp step."""
