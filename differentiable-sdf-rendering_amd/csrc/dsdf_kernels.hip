@@ -920,6 +920,14 @@ static int check_launch(const char *what) {
     return DSDF_OK;
 }
 
+// Launch plus check_launch.  The instantiations of a kernel template share one function type, so the call site picks one with
+// `cond ? k<true> : k<false>`; the arguments are converted to the kernel's parameter types (a plain nullptr will do).
+template <class... P, class... A>
+static int launch(const char *what, void (*k)(P...), dim3 grid, dim3 block, hipStream_t st, A &&...args) {
+    hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(args)...);
+    return check_launch(what);
+}
+
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Lane order of the general pass for this spp (see thread_lane) and the number of 64-thread units it launches per view.
@@ -1020,13 +1028,6 @@ static size_t cell_table_bytes(int rx, int ry, int rz) {
     return (n < ((uint64_t)1 << 32) && (uint64_t)(rx + 2 * DSDF_APRON) * (uint64_t)(ry + 2 * DSDF_APRON) < (1u << 23)) ? (size_t)n : 0;
 }
 
-// Largest number of views (<= DSDF_MAX_BATCH, <= n_views) one launch can take with this workspace.
-static int batch_size(int W, int H, int spp, int n_views, int integrator, size_t workspace_bytes, bool diff = true) {
-    int nv = n_views < DSDF_MAX_BATCH ? n_views : DSDF_MAX_BATCH;
-    while (nv > 1 && carve(nullptr, W, H, spp, nv, integrator, diff).bytes > workspace_bytes) --nv;
-    return nv;
-}
-
 static ViewArgs make_view_args(const dsdf_camera &cam, int W, int H, int spp, const float *offsets, uint32_t seed,
                                int integrator, int flags, const dsdf_params &prm, const float *emitter_u = nullptr,
                                const float *bsdf_u = nullptr, const float *lobe_u = nullptr) {
@@ -1042,7 +1043,93 @@ static ViewArgs make_view_args(const dsdf_camera &cam, int W, int H, int spp, co
     return A;
 }
 
-static ShadeArgs make_shade_args(const dsdf_shading *sh, bool with_grad) {
+// Parameters of a render pass.  The silhouette integrator consumes only the hit FLAG of a sample
+// (sdf_silhouette_reparam.py:20-22), never the hit distance, and the refinement loop
+// (shapes.py:245-257) cannot turn a hit into a miss: skipping it leaves every output unchanged.
+static dsdf_params pass_params(const dsdf_params &prm, int integrator) {
+    dsdf_params p = prm;
+    if (integrator == DSDF_SILHOUETTE) p.refine_steps = 0;
+    return p;
+}
+
+// One render call as its entry point received it (the argument list the render entry points of include/dsdf.h share) and what
+// follows from it; run_pass renders it one batch of views at a time, everything enqueued on `st`.
+struct PassCtx {
+    const char *name;      // the entry point, for its error texts
+    bool diff;             // gradient sweep: the workspace carries the backward queue and the film-block adjoint (carve)
+    const float *padded; int rx, ry, rz; const dsdf_params *prm; const dsdf_camera *cams; int n_views;
+    int W, H, spp; const float *offsets; const uint32_t *seeds; int integrator, flags; const dsdf_shading *shading;
+    void *workspace;
+    size_t ws_bytes;       // (what lies behind the carved part may hold the cell table of the direct primal)
+    hipStream_t st;
+    dsdf_params pp; bool direct;
+    const float *emitter_u, *bsdf_u, *lobe_u;
+    size_t Wb, Hb; uint32_t nl;
+    int row0, row1;        // film-block rows of this call (multi-GPU pixel-tile split; the whole film by default)
+    float *film;           // caller-owned film block to ACCUMULATE into (tile calls), or nullptr: the workspace's, zeroed
+    int64_t *stats;        // the caller's per-call counters, or nullptr
+    bool coef_beside;      // gradient sweep: k_backward_coef for the render kernel's own samples BESIDE the tail kernel, on a helper
+                           // stream, up to a snapshot of the queue lengths
+    bool coef_done_early;  // (set by run_pass when it did)
+
+    // view v0's part of a caller's (n_views, H, W, 3) image buffer
+    template <class T> T *image(T *base, int v0) const { return base + (size_t)v0 * W * H * 3; }
+};
+
+// (Null arguments are tolerated here: check_render_args, which every entry point calls next, refuses them.)
+static PassCtx make_ctx(const char *name, bool diff, const float *padded, int rx, int ry, int rz, const dsdf_params *prm,
+                        const dsdf_camera *cams, int n_views, int W, int H, int spp, const float *offsets, const uint32_t *seeds,
+                        int integrator, int flags, const dsdf_shading *shading, void *workspace, size_t workspace_bytes, void *stream) {
+    PassCtx c{};
+    c.name = name; c.diff = diff;
+    c.padded = padded; c.rx = rx; c.ry = ry; c.rz = rz; c.prm = prm; c.cams = cams; c.n_views = n_views;
+    c.W = W; c.H = H; c.spp = spp; c.offsets = offsets; c.seeds = seeds; c.integrator = integrator; c.flags = flags; c.shading = shading;
+    c.workspace = workspace; c.ws_bytes = workspace_bytes; c.st = (hipStream_t)stream;
+#if DSDF_XF
+    c.flags |= DSDF_NO_SKIP | DSDF_NO_HIT_PROOF;        // the per-pixel proofs reason in the cube's own frame: not in a world-space build
+#endif
+    if (prm) c.pp = pass_params(*prm, integrator);
+    c.direct = integrator == DSDF_DIRECT;
+    const dsdf_shading *sh = c.direct ? shading : nullptr;
+    c.emitter_u = sh ? sh->emitter_samples : nullptr;
+    c.bsdf_u = (sh && sh->use_mis) ? sh->bsdf_samples : nullptr;
+    c.lobe_u = (sh && sh->use_mis && sh->bsdf == 1) ? sh->bsdf_lobe_samples : nullptr;   // (n_views x lanes x 1)
+    c.Wb = W + 2 * DSDF_BORDER; c.Hb = H + 2 * DSDF_BORDER; c.nl = (uint32_t)(c.Wb * c.Hb * spp);
+    c.row0 = 0; c.row1 = (int)c.Hb; c.film = nullptr; c.stats = nullptr;
+    c.coef_beside = false; c.coef_done_early = false;
+    return c;
+}
+
+static GridView device_view(const PassCtx &c) { return device_view(c.padded, c.rx, c.ry, c.rz, *c.prm); }
+
+// The call's workspace carved for `nv` views per launch, and the largest such number (<= DSDF_MAX_BATCH, <= n_views) it can take.
+static Workspace carve(const PassCtx &c, int nv) { return carve(c.workspace, c.W, c.H, c.spp, nv, c.integrator, c.diff); }
+
+static int batch_size(const PassCtx &c) {
+    int nv = c.n_views < DSDF_MAX_BATCH ? c.n_views : DSDF_MAX_BATCH;
+    while (nv > 1 && carve(nullptr, c.W, c.H, c.spp, nv, c.integrator, c.diff).bytes > c.ws_bytes) --nv;
+    return nv;
+}
+
+static Queue make_queue(const PassCtx &c, const Workspace &ws) {
+    Queue q;
+    q.count = ws.count; q.lane = ws.qlane; q.rec = ws.qrec; q.rows = c.direct ? 27u : 9u; q.cap = ws.cap; q.nunits = ws.nunits;
+    q.coef = c.direct ? nullptr : ws.qcoef; q.coef_rows = ws.coef_rows;
+    return q;
+}
+
+// the view arguments of views [v0, v0 + nv) of the call
+static void fill_views(const PassCtx &c, int v0, int nv, ViewBatch &VB) {
+    for (int i = 0; i < nv; ++i) {
+        const size_t v = (size_t)(v0 + i);
+        VB.v[i] = make_view_args(c.cams[v], c.W, c.H, c.spp, c.offsets ? c.offsets + v * c.nl * 2 : nullptr, c.seeds ? c.seeds[v] : 0u,
+                                 c.integrator, c.flags, c.pp, c.emitter_u ? c.emitter_u + v * c.nl * 2 : nullptr,
+                                 c.bsdf_u ? c.bsdf_u + v * c.nl * 2 : nullptr, c.lobe_u ? c.lobe_u + v * c.nl : nullptr);
+    }
+}
+
+static ShadeArgs make_shade_args(const PassCtx &c, bool with_grad) {
+    const dsdf_shading *sh = c.shading;
     ShadeArgs S;
     memset(&S, 0, sizeof(S));
     if (sh) {
@@ -1057,28 +1144,24 @@ static ShadeArgs make_shade_args(const dsdf_shading *sh, bool with_grad) {
     }
     return S;
 }
-// Parameters of a render pass.  The silhouette integrator consumes only the hit FLAG of a sample
-// (sdf_silhouette_reparam.py:20-22), never the hit distance, and the refinement loop
-// (shapes.py:245-257) cannot turn a hit into a miss: skipping it leaves every output unchanged.
-static dsdf_params pass_params(const dsdf_params &prm, int integrator) {
-    dsdf_params p = prm;
-    if (integrator == DSDF_SILHOUETTE) p.refine_steps = 0;
-    return p;
+static int failf(int code, const PassCtx &c, const char *msg) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", c.name, msg);
+    return code;
 }
 
-static int check_render_args(const float *padded, int rx, int ry, int rz, const dsdf_params *prm,
-                             const dsdf_camera *cams, int n_views, int W, int H, int spp, int integrator,
-                             const dsdf_shading *shading, void *workspace, size_t workspace_bytes, bool diff) {
-    if (!padded || !prm || !cams || !workspace) return fail(DSDF_ERR_INVALID_ARG, "null pointer argument");
-    if (rx < 1 || ry < 1 || rz < 1 || n_views < 1 || W < 1 || H < 1 || spp < 1)
+// What every render entry point checks before any device work.  need_sampler: the call draws film samples (all but dsdf_grad_backward).
+static int check_render_args(const PassCtx &c, bool need_sampler) {
+    const dsdf_shading *shading = c.shading;
+    if (!c.padded || !c.prm || !c.cams || !c.workspace) return fail(DSDF_ERR_INVALID_ARG, "null pointer argument");
+    if (c.rx < 1 || c.ry < 1 || c.rz < 1 || c.n_views < 1 || c.W < 1 || c.H < 1 || c.spp < 1)
         return fail(DSDF_ERR_INVALID_ARG, "non-positive size argument");
-    if (integrator != DSDF_SILHOUETTE && integrator != DSDF_SIMPLE_SHADING && integrator != DSDF_DIRECT)
+    if (c.integrator != DSDF_SILHOUETTE && c.integrator != DSDF_SIMPLE_SHADING && c.integrator != DSDF_DIRECT)
         return fail(DSDF_ERR_INVALID_ARG, "unknown integrator id");
-    if (integrator == DSDF_DIRECT && (!shading || !shading->albedo || shading->ax < 1 || shading->ay < 1 || shading->az < 1))
+    if (c.direct && (!shading || !shading->albedo || shading->ax < 1 || shading->ay < 1 || shading->az < 1))
         return fail(DSDF_ERR_INVALID_ARG, "sdf_direct_reparam needs a dsdf_shading with an albedo volume");
-    if (integrator == DSDF_DIRECT && (shading->variant < 0 || shading->variant > 2))
+    if (c.direct && (shading->variant < 0 || shading->variant > 2))
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_shading.variant must be 0, 1 (detach_indirect_si) or 2 (decouple_reparam)");
-    if (integrator == DSDF_DIRECT && shading->bsdf != 0) {
+    if (c.direct && shading->bsdf != 0) {
         if (shading->bsdf != 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_shading.bsdf must be 0 (diffuse) or 1 (principled)");
         if (!shading->roughness || shading->rax < 1 || shading->ray < 1 || shading->raz < 1)
             return fail(DSDF_ERR_INVALID_ARG, "the principled BSDF needs dsdf_shading.roughness (raz,ray,rax,1)");
@@ -1088,10 +1171,10 @@ static int check_render_args(const float *padded, int rx, int ry, int rz, const 
                                               "(lib/variants/libdsdf_xf.so, -DDSDF_XF=1)");
 #endif
     }
-    size_t nl = (size_t)(W + 2 * DSDF_BORDER) * (H + 2 * DSDF_BORDER) * (size_t)spp;
     // reparam.py:48-50 wavefront-size limit
-    if (nl > 0x40000000ull) return fail(DSDF_ERR_INVALID_ARG, "wavefront size exceeds 0x40000000 lanes");
-    if (workspace_bytes < carve(nullptr, W, H, spp, 1, integrator, diff).bytes) return fail(DSDF_ERR_WORKSPACE, "workspace too small");
+    if (c.Wb * c.Hb * (size_t)c.spp > 0x40000000ull) return fail(DSDF_ERR_INVALID_ARG, "wavefront size exceeds 0x40000000 lanes");
+    if (c.ws_bytes < carve(nullptr, c.W, c.H, c.spp, 1, c.integrator, c.diff).bytes) return fail(DSDF_ERR_WORKSPACE, "workspace too small");
+    if (need_sampler && !c.offsets && !c.seeds) return failf(DSDF_ERR_INVALID_ARG, c, "need offsets or seeds");
     return DSDF_OK;
 }
 
@@ -1228,51 +1311,6 @@ size_t dsdf_forward_workspace_size(int width, int height, int spp, int n_views, 
 }
 
 }  // extern "C" (the shared host plumbing below is C++)
-
-// One batch of views of a render call: view arguments, per-pixel proofs, the render pass (primal or gradient sweep) into
-// ws.block.  Everything is enqueued on `st`.
-struct PassCtx {
-    const float *padded; int rx, ry, rz; const dsdf_params *prm; dsdf_params pp;
-    int W, H, spp, integrator, flags; bool direct;
-    const float *offsets, *emitter_u, *bsdf_u, *lobe_u; const uint32_t *seeds; const dsdf_shading *shading;
-    size_t Wb, Hb; uint32_t nl;
-    int row0, row1;        // film-block rows of this call (multi-GPU pixel-tile split; the whole film by default)
-    float *film;           // caller-owned film block to ACCUMULATE into (tile calls), or nullptr: the workspace's, zeroed
-    size_t ws_bytes;       // the caller's workspace (what lies behind the carved part may hold the cell table of the direct primal)
-    hipStream_t st;
-    bool coef_beside;      // gradient sweep: k_backward_coef for the render kernel's own samples BESIDE the tail kernel, on a helper
-                           // stream, up to a snapshot of the queue lengths
-    bool coef_done_early;  // (set by run_pass when it did)
-};
-
-static PassCtx make_ctx(const float *padded, int rx, int ry, int rz, const dsdf_params *prm, int W, int H, int spp,
-                        const float *offsets, const uint32_t *seeds, int integrator, int flags, const dsdf_shading *shading,
-                        void *stream) {
-    PassCtx c;
-    c.padded = padded; c.rx = rx; c.ry = ry; c.rz = rz; c.prm = prm; c.pp = pass_params(*prm, integrator);
-    c.W = W; c.H = H; c.spp = spp; c.integrator = integrator; c.flags = flags; c.direct = integrator == DSDF_DIRECT;
-#if DSDF_XF
-    c.flags |= DSDF_NO_SKIP | DSDF_NO_HIT_PROOF;        // the per-pixel proofs reason in the cube's own frame: not in a world-space build
-#endif
-    c.offsets = offsets; c.seeds = seeds; c.shading = shading; c.emitter_u = c.direct ? shading->emitter_samples : nullptr;
-    c.bsdf_u = (c.direct && shading->use_mis) ? shading->bsdf_samples : nullptr;
-    c.lobe_u = (c.direct && shading->use_mis && shading->bsdf == 1) ? shading->bsdf_lobe_samples : nullptr;   // (n_views x lanes x 1)
-    c.Wb = W + 2 * DSDF_BORDER; c.Hb = H + 2 * DSDF_BORDER; c.nl = (uint32_t)(c.Wb * c.Hb * spp);
-    c.row0 = 0; c.row1 = (int)c.Hb; c.film = nullptr; c.ws_bytes = 0;
-    c.st = (hipStream_t)stream;
-    c.coef_beside = false; c.coef_done_early = false;
-    return c;
-}
-
-// the view arguments of views [v0, v0 + nv) of the call
-static void fill_views(const PassCtx &c, const dsdf_camera *cams, int v0, int nv, ViewBatch &VB) {
-    for (int i = 0; i < nv; ++i) {
-        const size_t v = (size_t)(v0 + i);
-        VB.v[i] = make_view_args(cams[v], c.W, c.H, c.spp, c.offsets ? c.offsets + v * c.nl * 2 : nullptr, c.seeds ? c.seeds[v] : 0u,
-                                 c.integrator, c.flags, c.pp, c.emitter_u ? c.emitter_u + v * c.nl * 2 : nullptr,
-                                 c.bsdf_u ? c.bsdf_u + v * c.nl * 2 : nullptr, c.lobe_u ? c.lobe_u + v * c.nl : nullptr);
-    }
-}
 
 // persistent workers of k_render_items: enough single-wave blocks to fill every wave slot of the device
 static unsigned worker_blocks() {
@@ -1419,17 +1457,14 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     if (und && hipMemsetAsync(und, 0, sizeof(uint32_t), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(undecided list) failed");
     // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try)
     const float step0 = level > 0 ? skip_step(cams, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
-    hipLaunchKernelGGL(k_pixel_skip, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st,
-                       device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
-                       min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
-                       step0, step, hstep, und);
-    if (und)
-        hipLaunchKernelGGL(k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), dim3(256), 0, st,
-                           device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst,
-                           (const uint32_t *)und, (const uint32_t *)(und + DSDF_UNDECIDED_HDR), fstep);
-    if ((rc = check_launch("k_pixel_skip"))) return rc;
-    hipLaunchKernelGGL(k_skip_dilate, dim3((unsigned)((npix + 255) / 256), nv), dim3(256), 0, st, VB, dst);
-    if ((rc = check_launch("k_skip_dilate"))) return rc;
+    const dim3 pgrid((unsigned)((npix + 255) / 256), nv), blk(256);
+    if ((rc = launch("k_pixel_skip", k_pixel_skip, pgrid, blk, st, device_view(c), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
+                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und)))
+        return rc;
+    if (und && (rc = launch("k_pixel_hit_fine", k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), blk, st, device_view(c),
+                            fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, und, und + DSDF_UNDECIDED_HDR, fstep)))
+        return rc;
+    if ((rc = launch("k_skip_dilate", k_skip_dilate, pgrid, blk, st, VB, dst))) return rc;
     if (dst == sh.buf) {
         if (hipEventRecord(sh.ready, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipEventRecord(shared skip flags) failed");
         sh.valid = true; sh.padded = c.padded; sh.rx = c.rx; sh.ry = c.ry; sh.rz = c.rz; sh.W = c.W; sh.H = c.H; sh.nv = nv;
@@ -1461,15 +1496,10 @@ template <bool DIFF>
 static int prefill_film(const PassCtx &c, const Batch &b) {
     int rc;
     const dim3 grid((unsigned)((c.Wb * c.Hb + 255) / 256), b.nv), blk(256);
-    if (b.deep_skip) {
-        hipLaunchKernelGGL(k_film_ones, grid, blk, 0, c.st, b.VB, b.skip, b.film, c.row0, c.row1, b.st64);
-        if ((rc = check_launch("k_film_ones"))) return rc;
-    }
-    if (b.env_fill) {
-        hipLaunchKernelGGL(k_film_env, grid, blk, 0, c.st, b.VB, b.skip, b.film, c.row0, c.row1,
-                           DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY, b.S.env[0], b.S.env[1], b.S.env[2]);
-        if ((rc = check_launch("k_film_env"))) return rc;
-    }
+    if (b.deep_skip && (rc = launch("k_film_ones", k_film_ones, grid, blk, c.st, b.VB, b.skip, b.film, c.row0, c.row1, b.st64))) return rc;
+    if (b.env_fill && (rc = launch("k_film_env", k_film_env, grid, blk, c.st, b.VB, b.skip, b.film, c.row0, c.row1,
+                                   DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY, b.S.env[0], b.S.env[1], b.S.env[2])))
+        return rc;
     return DSDF_OK;
 }
 
@@ -1508,9 +1538,9 @@ static int persistent_pass(PassCtx &c, const Workspace &ws, const Batch &b, bool
         return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tail queue) failed");
     uint32_t *hdr = ws.items;
     uint32_t *list = ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR;
-    hipLaunchKernelGGL(k_build_items, dim3((unsigned)(((size_t)nv * O.per_view + DSDF_ITEM_REGION - 1) / DSDF_ITEM_REGION)), dim3(256), 0, st,
-                       b.VB, 0, nv, b.skip, far_bit, c.row0, c.row1, O, hdr, list);
-    if ((rc = check_launch("k_build_items"))) return rc;
+    if ((rc = launch("k_build_items", k_build_items, dim3((unsigned)(((size_t)nv * O.per_view + DSDF_ITEM_REGION - 1) / DSDF_ITEM_REGION)), dim3(256), st,
+                     b.VB, 0, nv, b.skip, far_bit, c.row0, c.row1, O, hdr, list)))
+        return rc;
     TailQueue tq;
     memset(&tq, 0, sizeof(tq));
     if (handoff) {
@@ -1527,18 +1557,15 @@ static int persistent_pass(PassCtx &c, const Workspace &ws, const Batch &b, bool
     // (the default fills every wave slot of the device, workers that find no slot start when others retire)
     const dim3 grid(worker_blocks()), blk(64);
     timing_mark(0, st);
-    if (wavefront) {
+    if (wavefront)
         // the march of the primary rays into hit_t / the record rows (its tail kernel below); direct_wavefront does the rest
-        if (st64) hipLaunchKernelGGL((k_render_items_store<DIFF, true>), grid, blk, 0, st, G, c.pp, b.VB, q, st64, b.skip, S, tq, hdr, list, ws.hit_t);
-        else hipLaunchKernelGGL((k_render_items_store<DIFF, false>), grid, blk, 0, st, G, c.pp, b.VB, q, st64, b.skip, S, tq, hdr, list, ws.hit_t);
-    } else if (c.direct) {
-        if (st64) hipLaunchKernelGGL((k_render_items<DIFF, true, true>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
-        else hipLaunchKernelGGL((k_render_items<DIFF, true, false>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
-    } else {
-        if (st64) hipLaunchKernelGGL((k_render_items<DIFF, false, true>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
-        else hipLaunchKernelGGL((k_render_items<DIFF, false, false>), grid, blk, 0, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
-    }
-    if ((rc = check_launch("k_render_items"))) return rc;
+        rc = launch("k_render_items", st64 ? k_render_items_store<DIFF, true> : k_render_items_store<DIFF, false>, grid, blk, st,
+                    G, c.pp, b.VB, q, st64, b.skip, S, tq, hdr, list, ws.hit_t);
+    else
+        rc = launch("k_render_items", c.direct ? (st64 ? k_render_items<DIFF, true, true> : k_render_items<DIFF, true, false>)
+                                               : (st64 ? k_render_items<DIFF, false, true> : k_render_items<DIFF, false, false>),
+                    grid, blk, st, G, c.pp, b.VB, b.film, q, st64, b.skip, S, tq, hdr, list);
+    if (rc) return rc;
     timing_mark(1, st);
     if (!handoff) return DSDF_OK;
     bool coef_beside = false;
@@ -1556,20 +1583,17 @@ static int persistent_pass(PassCtx &c, const Workspace &ws, const Batch &b, bool
         if (!coef_fork || hipEventRecord(coef_fork, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
     }
     const dim3 tgrid(DSDF_TAIL_SUBQ * DSDF_TAIL_BLOCKS_PER_SUBQ), tblk(256);
-    unsigned long long *tst = st64 ? st64 : g_tail_stats;
-    if (DIFF && wavefront) hipLaunchKernelGGL((k_tail_trace_diff<true>), tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, q, (unsigned long long *)nullptr);
-    else if (DIFF) hipLaunchKernelGGL((k_tail_trace_diff<false>), tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, q, tst);
-    else hipLaunchKernelGGL(k_tail_trace_plain, tgrid, tblk, 0, st, G, c.pp, b.VB, b.film, tq, wavefront ? (unsigned long long *)nullptr : tst,
-                            wavefront ? ws.hit_t : (float *)nullptr);
-    if ((rc = check_launch("k_tail_trace"))) return rc;
+    unsigned long long *tst = wavefront ? nullptr : (st64 ? st64 : g_tail_stats);
+    if (DIFF) rc = launch("k_tail_trace", wavefront ? k_tail_trace_diff<true> : k_tail_trace_diff<false>, tgrid, tblk, st, G, c.pp, b.VB, b.film, tq, q, tst);
+    else rc = launch("k_tail_trace", k_tail_trace_plain, tgrid, tblk, st, G, c.pp, b.VB, b.film, tq, tst, wavefront ? ws.hit_t : nullptr);
+    if (rc) return rc;
     if (coef_beside) {
         // ... and the coefficients of the samples the render kernel queued itself on the helper stream, beside the tail kernel
         // (it waits for the render kernel and the copy above); the caller's stream joins it
         hipStream_t cs = hs[1];
         if (hipStreamWaitEvent(cs, coef_fork, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream fork failed");
         const dim3 cgrid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
-        hipLaunchKernelGGL(k_backward_coef, cgrid, dim3(64), 0, cs, G, c.pp, b.VB, q, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)ws.count0);
-        if ((rc = check_launch("k_backward_coef"))) return rc;
+        if ((rc = launch("k_backward_coef", k_backward_coef, cgrid, dim3(64), cs, G, c.pp, b.VB, q, nullptr, nullptr, ws.count0))) return rc;
         hipEvent_t join = next_event();
         if (!join || hipEventRecord(join, cs) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "coefficient stream join failed");
         c.coef_done_early = true;
@@ -1593,28 +1617,23 @@ static int direct_wavefront(const PassCtx &c, const Workspace &ws, const Batch &
     const dim3 grid(worker_blocks()), blk(64), sgrid(DSDF_TAIL_SUBQ * DSDF_SHQ_BLOCKS_PER_SUBQ), sblk(256);
     if (hipMemsetAsync(ws.shq, 0, scnt, st) != hipSuccess || hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess)
         return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(shadow queue) failed");
-    hipLaunchKernelGGL((k_direct_items<0, DIFF>), grid, blk, 0, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q);
-    if ((rc = check_launch("k_direct_items<0>"))) return rc;
+    if ((rc = launch("k_direct_items<0>", k_direct_items<0, DIFF>, grid, blk, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q))) return rc;
     if (DIFF) {
-        hipLaunchKernelGGL(k_shadow_stream_diff, sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, b.q, b.st64);
-        if ((rc = check_launch("k_shadow_stream_diff"))) return rc;
+        if ((rc = launch("k_shadow_stream_diff", k_shadow_stream_diff, sgrid, sblk, st, b.G, c.pp, b.VB, sq, b.q, b.st64))) return rc;
     } else {
         // the cell table the shadow rays read, behind the carved workspace when the caller provided the room (dsdf_cell_table_size)
         const size_t tb = cell_table_enabled() ? cell_table_bytes(c.rx, c.ry, c.rz) : 0;
         const size_t toff = align_up(ws.bytes, 256);
         float *table = (tb && c.ws_bytes >= toff + tb) ? (float *)((char *)ws.block + toff) : nullptr;
-        if (table) {
-            hipLaunchKernelGGL(k_cell_table, dim3(16384), dim3(256), 0, st, c.padded, c.rx + 2 * DSDF_APRON, c.ry + 2 * DSDF_APRON, c.rz + 2 * DSDF_APRON, table);
-            if ((rc = check_launch("k_cell_table"))) return rc;
-            hipLaunchKernelGGL((k_shadow_stream<true>), sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, ws.hit_t, b.st64, (const float *)table);
-        } else {
-            hipLaunchKernelGGL((k_shadow_stream<false>), sgrid, sblk, 0, st, b.G, c.pp, b.VB, sq, ws.hit_t, b.st64, (const float *)nullptr);
-        }
-        if ((rc = check_launch("k_shadow_stream"))) return rc;
+        if (table && (rc = launch("k_cell_table", k_cell_table, dim3(16384), dim3(256), st, c.padded, c.rx + 2 * DSDF_APRON, c.ry + 2 * DSDF_APRON,
+                                  c.rz + 2 * DSDF_APRON, table)))
+            return rc;
+        if ((rc = launch("k_shadow_stream", table ? k_shadow_stream<true> : k_shadow_stream<false>, sgrid, sblk, st, b.G, c.pp, b.VB, sq, ws.hit_t,
+                         b.st64, table)))
+            return rc;
     }
     if (hipMemsetAsync(hdr + 16, 0, tick_bytes, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tickets) failed");
-    hipLaunchKernelGGL((k_direct_items<1, DIFF>), grid, blk, 0, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q);
-    return check_launch("k_direct_items<1>");
+    return launch("k_direct_items<1>", k_direct_items<1, DIFF>, grid, blk, st, b.G, c.pp, b.VB, b.film, b.skip, b.S, sq, hdr, list, ws.hit_t, b.q);
 }
 
 // Stage 3 for the other sample counts: k_render_pass, one lane per sample.
@@ -1626,29 +1645,27 @@ static int lane_pass(const PassCtx &c, const Batch &b) {
     M.n_lanes = c.nl; M.row0 = c.row0; M.row1 = c.row1; M.deep_mask = b.deep_skip ? DSDF_PX_DEEP : 0u; M.env_fill = b.env_fill ? 1 : 0;
     const dim3 grid((unsigned)(nunits / 4), b.nv), blk(DSDF_BLOCK);
     timing_mark(0, c.st);
-    if (c.direct) hipLaunchKernelGGL((k_render_pass<DIFF, true>), grid, blk, 0, c.st, b.G, c.pp, b.VB, b.film, b.q, b.st64, M, b.skip, b.S);
-    else hipLaunchKernelGGL((k_render_pass<DIFF, false>), grid, blk, 0, c.st, b.G, c.pp, b.VB, b.film, b.q, b.st64, M, b.skip, b.S);
-    int rc = check_launch("k_render_pass");
+    const int rc = launch("k_render_pass", c.direct ? k_render_pass<DIFF, true> : k_render_pass<DIFF, false>, grid, blk, c.st,
+                          b.G, c.pp, b.VB, b.film, b.q, b.st64, M, b.skip, b.S);
     if (rc) return rc;
     timing_mark(1, c.st);
     return DSDF_OK;
 }
 
 template <bool DIFF>
-static int run_pass(PassCtx &c, const Workspace &ws, const dsdf_camera *cams, int v0, int nv, ViewBatch &VB, Queue q,
-                    int64_t *stats) {
+static int run_pass(PassCtx &c, const Workspace &ws, int v0, int nv, ViewBatch &VB, Queue q) {
     int rc;
-    fill_views(c, cams, v0, nv, VB);
+    fill_views(c, v0, nv, VB);
     const size_t nch = (size_t)film_channels(c.integrator), npix = c.Wb * c.Hb;
     float *film = c.film ? c.film + (size_t)v0 * npix * nch : ws.block;
     if (!c.film && hipMemsetAsync(ws.block, 0, nv * npix * nch * sizeof(float), c.st) != hipSuccess)
         return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(film block) failed");
     const unsigned char *skip;
-    if ((rc = pixel_proof(c, ws, cams + v0, nv, VB, skip))) return rc;
-    const ShadeArgs S = make_shade_args(c.shading, DIFF);
+    if ((rc = pixel_proof(c, ws, c.cams + v0, nv, VB, skip))) return rc;
+    const ShadeArgs S = make_shade_args(c, DIFF);
     const bool deep_skip = !DIFF && skip && c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF);
     const bool env_fill = c.direct && skip && !S.hide_emitters;
-    const Batch b = {VB, nv, device_view(c.padded, c.rx, c.ry, c.rz, *c.prm), S, q, film, skip, (unsigned long long *)stats, deep_skip, env_fill};
+    const Batch b = {VB, nv, device_view(c), S, q, film, skip, (unsigned long long *)c.stats, deep_skip, env_fill};
     if ((rc = prefill_film<DIFF>(c, b))) return rc;
     if (c.spp % 64 == 0) {
         // sdf_direct_reparam's primary rays as a wavefront (DSDF_DIRECT_WAVEFRONT=0: the fused worker; use_mis keeps it)
@@ -1659,18 +1676,40 @@ static int run_pass(PassCtx &c, const Workspace &ws, const dsdf_camera *cams, in
     return lane_pass<DIFF>(c, b);
 }
 
-static Queue make_queue(const Workspace &ws, bool direct) {
-    Queue q;
-    q.count = ws.count; q.lane = ws.qlane; q.rec = ws.qrec; q.rows = direct ? 27u : 9u; q.cap = ws.cap; q.nunits = ws.nunits;
-    q.coef = direct ? nullptr : ws.qcoef; q.coef_rows = ws.coef_rows;
-    return q;
+// The views of the call in batches of as many as its workspace takes per launch: run_pass, then what the entry point does with
+// the batch, `tail(ws, q, VB, v0, nv)`.
+template <bool DIFF, class Tail>
+static int for_each_batch(PassCtx &c, Tail tail) {
+    const int nb = batch_size(c);
+    const Workspace ws = carve(c, nb);
+    const Queue q = make_queue(c, ws);
+    for (int v0 = 0; v0 < c.n_views; v0 += nb) {
+        const int nv = (c.n_views - v0) < nb ? (c.n_views - v0) : nb;
+        ViewBatch VB;
+        int rc;
+        if ((rc = run_pass<DIFF>(c, ws, v0, nv, VB, q))) return rc;
+        if ((rc = tail(ws, q, VB, v0, nv))) return rc;
+    }
+    return DSDF_OK;
 }
 
-static int develop_batch(const PassCtx &c, const Workspace &ws, int nv, float *image) {
-    const dim3 grid((c.W * c.H + 255) / 256, nv);
-    if (c.direct) hipLaunchKernelGGL(k_develop_rgb, grid, dim3(256), 0, c.st, ws.block, c.W, c.H, image);
-    else hipLaunchKernelGGL(k_develop, grid, dim3(256), 0, c.st, ws.block, c.W, c.H, image);
-    return check_launch("k_develop");
+// `HDRFilm.develop` of nv film blocks
+static int develop(const float *film, int nv, int W, int H, bool direct, float *image, hipStream_t st) {
+    return launch("k_develop", direct ? k_develop_rgb : k_develop, dim3((W * H + 255) / 256, nv), dim3(256), st, film, W, H, image);
+}
+
+// The backward proper of a batch: the film adjoint of `film` under the image gradient, then the queued samples against it.
+// apply_coef: the adjoint coefficients of the samples are in the queue (dsdf_grad_sweep), k_backward_apply only applies them.
+static int backward_batch(const PassCtx &c, const Workspace &ws, const Queue &q, const ViewBatch &VB, int nv, const float *film,
+                          const float *grad_image, float *grad_grid, float *grad_p, int64_t *stats, bool apply_coef) {
+    int rc;
+    if ((rc = launch("k_develop_adjoint", c.direct ? k_develop_adjoint_rgb : k_develop_adjoint, dim3((unsigned)((c.Wb * c.Hb + 255) / 256), nv),
+                     dim3(256), c.st, film, grad_image, c.W, c.H, ws.block_adj)))
+        return rc;
+    const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
+    if (apply_coef) return launch("k_backward", k_backward_apply, grid, dim3(64), c.st, device_view(c), c.pp, VB, q, ws.block_adj, grad_grid);
+    return launch("k_backward", c.direct ? k_backward<true> : k_backward<false>, grid, dim3(64), c.st, device_view(c), c.pp, VB, q,
+                  ws.block_adj, grad_grid, grad_p, (unsigned long long *)stats, make_shade_args(c, true));
 }
 
 extern "C" {
@@ -1679,23 +1718,15 @@ int dsdf_render_forward(const float *padded, int rx, int ry, int rz, const dsdf_
                         int n_views, int width, int height, int spp, const float *offsets, const uint32_t *seeds,
                         int integrator, int flags, const dsdf_shading *shading, float *image_out, void *workspace,
                         size_t workspace_bytes, int64_t *stats, void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, false);
+    PassCtx c = make_ctx("dsdf_render_forward", false, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, true);
     if (rc) return rc;
-    if (!image_out) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward: image_out is null");
-    if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward: need offsets or seeds");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    c.ws_bytes = workspace_bytes;
-    const int nb = batch_size(width, height, spp, n_views, integrator, workspace_bytes, false);
-    const Workspace ws = carve(workspace, width, height, spp, nb, integrator, false);
-    const Queue q = make_queue(ws, c.direct);
-    for (int v0 = 0; v0 < n_views; v0 += nb) {
-        const int nv = (n_views - v0) < nb ? (n_views - v0) : nb;
-        ViewBatch VB;
-        if ((rc = run_pass<false>(c, ws, cams, v0, nv, VB, q, stats))) return rc;
-        if ((rc = develop_batch(c, ws, nv, image_out + (size_t)v0 * width * height * 3))) return rc;
-    }
-    return DSDF_OK;
+    if (!image_out) return failf(DSDF_ERR_INVALID_ARG, c, "image_out is null");
+    c.stats = stats;
+    return for_each_batch<false>(c, [&](const Workspace &ws, const Queue &, const ViewBatch &, int v0, int nv) {
+        return develop(ws.block, nv, c.W, c.H, c.direct, c.image(image_out, v0), c.st);
+    });
 }
 
 int dsdf_render_backward(const float *padded, int rx, int ry, int rz, const dsdf_params *prm, const dsdf_camera *cams,
@@ -1703,77 +1734,48 @@ int dsdf_render_backward(const float *padded, int rx, int ry, int rz, const dsdf
                          int integrator, int flags, const dsdf_shading *shading, const float *grad_image, float *grad_grid,
                          float *grad_p, float *image_out, void *workspace, size_t workspace_bytes, int64_t *stats,
                          void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, true);
+    PassCtx c = make_ctx("dsdf_render_backward", true, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, true);
     if (rc) return rc;
-    if (!grad_image || !grad_grid) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_backward: null gradient buffer");
-    if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_backward: need offsets or seeds");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    hipStream_t st = c.st;
-    const int nb = batch_size(width, height, spp, n_views, integrator, workspace_bytes, true);
-    const Workspace ws = carve(workspace, width, height, spp, nb, integrator, true);
-    const Queue q = make_queue(ws, c.direct);
-    const GridView G = device_view(padded, rx, ry, rz, *prm);
-    const ShadeArgs S = make_shade_args(shading, true);
-    for (int v0 = 0; v0 < n_views; v0 += nb) {
-        const int nv = (n_views - v0) < nb ? (n_views - v0) : nb;
-        ViewBatch VB;
-        if ((rc = run_pass<true>(c, ws, cams, v0, nv, VB, q, stats))) return rc;
-        if (image_out && (rc = develop_batch(c, ws, nv, image_out + (size_t)v0 * width * height * 3))) return rc;
-        const dim3 adj_grid((unsigned)((c.Wb * c.Hb + 255) / 256), nv);
-        const float *gi = grad_image + (size_t)v0 * width * height * 3;
-        if (c.direct) hipLaunchKernelGGL(k_develop_adjoint_rgb, adj_grid, dim3(256), 0, st, ws.block, gi, width, height, ws.block_adj);
-        else hipLaunchKernelGGL(k_develop_adjoint, adj_grid, dim3(256), 0, st, ws.block, gi, width, height, ws.block_adj);
-        if ((rc = check_launch("k_develop_adjoint"))) return rc;
-        const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
-        unsigned long long *st64 = (unsigned long long *)stats;
-        if (c.direct) hipLaunchKernelGGL(k_backward<true>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, st64, S);
-        else hipLaunchKernelGGL(k_backward<false>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, st64, S);
-        if ((rc = check_launch("k_backward"))) return rc;
-    }
-    return DSDF_OK;
+    if (!grad_image || !grad_grid) return failf(DSDF_ERR_INVALID_ARG, c, "null gradient buffer");
+    c.stats = stats;
+    return for_each_batch<true>(c, [&](const Workspace &ws, const Queue &q, const ViewBatch &VB, int v0, int nv) {
+        int rc;
+        if (image_out && (rc = develop(ws.block, nv, c.W, c.H, c.direct, c.image(image_out, v0), c.st))) return rc;
+        return backward_batch(c, ws, q, VB, nv, ws.block, c.image(grad_image, v0), grad_grid, grad_p, stats, false);
+    });
 }
 
 int dsdf_render_forward_grad(const float *padded, int rx, int ry, int rz, const dsdf_params *prm, const dsdf_camera *cams,
                              int n_views, int width, int height, int spp, const float *offsets, const uint32_t *seeds,
                              int integrator, int flags, const dsdf_shading *shading, const float *tangent_padded, const float *tangent_p,
                              float *grad_image_out, float *image_out, void *workspace, size_t workspace_bytes, void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, true);
+    PassCtx c = make_ctx("dsdf_render_forward_grad", true, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, true);
     if (rc) return rc;
-    if (!grad_image_out) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward_grad: grad_image_out is null");
-    if (integrator == DSDF_DIRECT && shading->bsdf == 1 && shading->use_mis)
-        return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward_grad: forward mode is not provided for the principled BSDF with use_mis");
-    if (!tangent_padded && !tangent_p) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward_grad: need a tangent");
-    if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_forward_grad: need offsets or seeds");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    hipStream_t st = c.st;
-    const int nb = batch_size(width, height, spp, n_views, integrator, workspace_bytes, true);
-    const Workspace ws = carve(workspace, width, height, spp, nb, integrator, true);
-    const Queue q = make_queue(ws, c.direct);
-    const GridView G = device_view(padded, rx, ry, rz, *prm);
-    const ShadeArgs S = make_shade_args(shading, false);
+    if (!grad_image_out) return failf(DSDF_ERR_INVALID_ARG, c, "grad_image_out is null");
+    if (c.direct && shading->bsdf == 1 && shading->use_mis)
+        return failf(DSDF_ERR_INVALID_ARG, c, "forward mode is not provided for the principled BSDF with use_mis");
+    if (!tangent_padded && !tangent_p) return failf(DSDF_ERR_INVALID_ARG, c, "need a tangent");
+    const GridView G = device_view(c);
+    const ShadeArgs S = make_shade_args(c, false);
     const size_t nch = (size_t)film_channels(integrator);
     const V3 dp = tangent_p ? mk(tangent_p[0], tangent_p[1], tangent_p[2]) : mk(0.f, 0.f, 0.f);
-    for (int v0 = 0; v0 < n_views; v0 += nb) {
-        const int nv = (n_views - v0) < nb ? (n_views - v0) : nb;
-        ViewBatch VB;
-        if ((rc = run_pass<true>(c, ws, cams, v0, nv, VB, q, nullptr))) return rc;
+    return for_each_batch<true>(c, [&](const Workspace &ws, const Queue &q, const ViewBatch &VB, int v0, int nv) {
+        int rc;
         // the tangent film block lives in the adjoint block's storage
-        if (hipMemsetAsync(ws.block_adj, 0, nv * c.Wb * c.Hb * nch * sizeof(float), st) != hipSuccess)
+        if (hipMemsetAsync(ws.block_adj, 0, nv * c.Wb * c.Hb * nch * sizeof(float), c.st) != hipSuccess)
             return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(tangent block) failed");
-        const dim3 tgrid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv);
-        if (c.direct) hipLaunchKernelGGL(k_forward_tangent<true>, tgrid, dim3(64), 0, st, G, tangent_padded, dp, c.pp, VB, q, ws.block_adj, S);
-        else hipLaunchKernelGGL(k_forward_tangent<false>, tgrid, dim3(64), 0, st, G, tangent_padded, dp, c.pp, VB, q, ws.block_adj, S);
-        if ((rc = check_launch("k_forward_tangent"))) return rc;
-        const dim3 dev_grid((width * height + 255) / 256, nv);
-        float *gout = grad_image_out + (size_t)v0 * width * height * 3;
-        if (c.direct) hipLaunchKernelGGL(k_develop_tangent_rgb, dev_grid, dim3(256), 0, st, ws.block, ws.block_adj, width, height, gout);
-        else hipLaunchKernelGGL(k_develop_tangent, dev_grid, dim3(256), 0, st, ws.block, ws.block_adj, width, height, gout);
-        if ((rc = check_launch("k_develop_tangent"))) return rc;
-        if (image_out && (rc = develop_batch(c, ws, nv, image_out + (size_t)v0 * width * height * 3))) return rc;
-    }
-    return DSDF_OK;
+        if ((rc = launch("k_forward_tangent", c.direct ? k_forward_tangent<true> : k_forward_tangent<false>,
+                         dim3((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, nv), dim3(64), c.st, G, tangent_padded, dp, c.pp, VB, q, ws.block_adj, S)))
+            return rc;
+        if ((rc = launch("k_develop_tangent", c.direct ? k_develop_tangent_rgb : k_develop_tangent, dim3((c.W * c.H + 255) / 256, nv), dim3(256), c.st,
+                         ws.block, ws.block_adj, c.W, c.H, c.image(grad_image_out, v0))))
+            return rc;
+        return image_out ? develop(ws.block, nv, c.W, c.H, c.direct, c.image(image_out, v0), c.st) : DSDF_OK;
+    });
 }
 
 // ---- multi-GPU pixel-tile split: when there are more ranks than views, a view is cut into row windows of
@@ -1781,8 +1783,10 @@ int dsdf_render_forward_grad(const float *padded, int rx, int ry, int rz, const 
 // across the ranks of the view (one RCCL all-reduce, dsdf/parallel.py) and developed; the gradient pass does the same for
 // its film, then every rank back-propagates ITS samples against the summed film.  Samples keep their reference lane
 // index, so the union over the windows is sample for sample the un-split render.
-static int check_rows(int height, int row0, int row1) {
-    if (row0 < 0 || row1 > height + 2 * DSDF_BORDER || row0 >= row1) return fail(DSDF_ERR_INVALID_ARG, "bad film-block row window");
+static int set_window(PassCtx &c, int row0, int row1, float *film) {
+    if (row0 < 0 || row1 > c.H + 2 * DSDF_BORDER || row0 >= row1) return fail(DSDF_ERR_INVALID_ARG, "bad film-block row window");
+    if (!film) return failf(DSDF_ERR_INVALID_ARG, c, "film is null");
+    c.row0 = row0; c.row1 = row1; c.film = film;
     return DSDF_OK;
 }
 
@@ -1790,31 +1794,18 @@ int dsdf_render_film(const float *padded, int rx, int ry, int rz, const dsdf_par
                      int n_views, int width, int height, int spp, const float *offsets, const uint32_t *seeds,
                      int integrator, int flags, const dsdf_shading *shading, int row0, int row1, float *film,
                      void *workspace, size_t workspace_bytes, int64_t *stats, void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, false);
+    PassCtx c = make_ctx("dsdf_render_film", false, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, true);
     if (rc) return rc;
-    if ((rc = check_rows(height, row0, row1))) return rc;
-    if (!film) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_film: film is null");
-    if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_render_film: need offsets or seeds");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    c.row0 = row0; c.row1 = row1; c.film = film; c.ws_bytes = workspace_bytes;
-    const int nb = batch_size(width, height, spp, n_views, integrator, workspace_bytes, false);
-    const Workspace ws = carve(workspace, width, height, spp, nb, integrator, false);
-    const Queue q = make_queue(ws, c.direct);
-    for (int v0 = 0; v0 < n_views; v0 += nb) {
-        const int nv = (n_views - v0) < nb ? (n_views - v0) : nb;
-        ViewBatch VB;
-        if ((rc = run_pass<false>(c, ws, cams, v0, nv, VB, q, stats))) return rc;
-    }
-    return DSDF_OK;
+    if ((rc = set_window(c, row0, row1, film))) return rc;
+    c.stats = stats;
+    return for_each_batch<false>(c, [](const Workspace &, const Queue &, const ViewBatch &, int, int) { return DSDF_OK; });
 }
 
 int dsdf_develop(const float *film, int n_views, int width, int height, int integrator, float *image_out, void *stream) {
     if (!film || !image_out || n_views < 1 || width < 1 || height < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_develop: bad argument");
-    const dim3 grid((width * height + 255) / 256, n_views);
-    if (integrator == DSDF_DIRECT) hipLaunchKernelGGL(k_develop_rgb, grid, dim3(256), 0, (hipStream_t)stream, film, width, height, image_out);
-    else hipLaunchKernelGGL(k_develop, grid, dim3(256), 0, (hipStream_t)stream, film, width, height, image_out);
-    return check_launch("k_develop");
+    return develop(film, n_views, width, height, integrator == DSDF_DIRECT, image_out, (hipStream_t)stream);
 }
 
 int dsdf_sampler_2d(const uint32_t *seeds, int n_views, int width, int height, int spp, int mirror, float *offsets_out, void *stream) {
@@ -1871,29 +1862,25 @@ int dsdf_grad_sweep(const float *padded, int rx, int ry, int rz, const dsdf_para
                     int n_views, int width, int height, int spp, const float *offsets, const uint32_t *seeds,
                     int integrator, int flags, const dsdf_shading *shading, int row0, int row1, float *film,
                     void *workspace, size_t workspace_bytes, void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, true);
+    PassCtx c = make_ctx("dsdf_grad_sweep", true, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, true);
     if (rc) return rc;
-    if ((rc = check_rows(height, row0, row1))) return rc;
-    if (!film) return fail(DSDF_ERR_INVALID_ARG, "dsdf_grad_sweep: film is null");
-    if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_grad_sweep: need offsets or seeds");
-    if (batch_size(width, height, spp, n_views, integrator, workspace_bytes, true) < n_views)
+    if ((rc = set_window(c, row0, row1, film))) return rc;
+    if (batch_size(c) < n_views)
         return fail(DSDF_ERR_WORKSPACE, "dsdf_grad_sweep: the workspace must hold all views of the call (the backward queue stays in it)");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    c.row0 = row0; c.row1 = row1; c.film = film;
-    const Workspace ws = carve(workspace, width, height, spp, n_views, integrator, true);
+    const Workspace ws = carve(c, n_views);
     ViewBatch VB;
-    const Queue q = make_queue(ws, c.direct);
+    const Queue q = make_queue(c, ws);
     c.coef_beside = q.coef != nullptr;
-    if ((rc = run_pass<true>(c, ws, cams, 0, n_views, VB, q, nullptr))) return rc;
+    if ((rc = run_pass<true>(c, ws, 0, n_views, VB, q))) return rc;
     if (q.coef) {
         // the image-independent half of the adjoint of the queued samples, now: the caller has the primal pass to run (or
         // running on another stream) before it can hand over the image gradient.  (If run_pass already did the render kernel's
         // own samples beside the tail kernel, only what the tail kernel appended is left.)
         const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, n_views);
-        hipLaunchKernelGGL(k_backward_coef, grid, dim3(64), 0, c.st, device_view(padded, rx, ry, rz, *prm), c.pp, VB, q,
-                           (const uint32_t *)(c.coef_done_early ? ws.count0 : nullptr), (uint32_t *)nullptr, (const uint32_t *)nullptr);
-        return check_launch("k_backward_coef");
+        return launch("k_backward_coef", k_backward_coef, grid, dim3(64), c.st, device_view(c), c.pp, VB, q,
+                      c.coef_done_early ? ws.count0 : nullptr, nullptr, nullptr);
     }
     return DSDF_OK;
 }
@@ -1903,29 +1890,19 @@ int dsdf_grad_backward(const float *padded, int rx, int ry, int rz, const dsdf_p
                        int integrator, int flags, const dsdf_shading *shading, const float *film_total,
                        const float *grad_image, float *grad_grid, float *grad_p, void *workspace, size_t workspace_bytes,
                        void *stream) {
-    int rc = check_render_args(padded, rx, ry, rz, prm, cams, n_views, width, height, spp, integrator, shading, workspace,
-                               workspace_bytes, true);
+    PassCtx c = make_ctx("dsdf_grad_backward", true, padded, rx, ry, rz, prm, cams, n_views, width, height, spp, offsets, seeds,
+                         integrator, flags, shading, workspace, workspace_bytes, stream);
+    int rc = check_render_args(c, false);          // (the samples are in the queue: no sampler is needed)
     if (rc) return rc;
-    if (!film_total || !grad_image || !grad_grid) return fail(DSDF_ERR_INVALID_ARG, "dsdf_grad_backward: null buffer");
-    if (batch_size(width, height, spp, n_views, integrator, workspace_bytes, true) < n_views)
+    if (!film_total || !grad_image || !grad_grid) return failf(DSDF_ERR_INVALID_ARG, c, "null buffer");
+    if (batch_size(c) < n_views)
         return fail(DSDF_ERR_WORKSPACE, "dsdf_grad_backward: the workspace must be the one dsdf_grad_sweep filled");
-    PassCtx c = make_ctx(padded, rx, ry, rz, prm, width, height, spp, offsets, seeds, integrator, flags, shading, stream);
-    hipStream_t st = c.st;
-    const Workspace ws = carve(workspace, width, height, spp, n_views, integrator, true);
-    const Queue q = make_queue(ws, c.direct);
+    const Workspace ws = carve(c, n_views);
+    const Queue q = make_queue(c, ws);
     ViewBatch VB;
-    fill_views(c, cams, 0, n_views, VB);
-    const dim3 adj_grid((unsigned)((c.Wb * c.Hb + 255) / 256), n_views);
-    if (c.direct) hipLaunchKernelGGL(k_develop_adjoint_rgb, adj_grid, dim3(256), 0, st, film_total, grad_image, width, height, ws.block_adj);
-    else hipLaunchKernelGGL(k_develop_adjoint, adj_grid, dim3(256), 0, st, film_total, grad_image, width, height, ws.block_adj);
-    if ((rc = check_launch("k_develop_adjoint"))) return rc;
-    const GridView G = device_view(padded, rx, ry, rz, *prm);
-    const ShadeArgs S = make_shade_args(shading, true);
-    const dim3 grid((ws.nunits + DSDF_BWD_UNITS - 1) / DSDF_BWD_UNITS, n_views);
-    if (c.direct) hipLaunchKernelGGL(k_backward<true>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, (unsigned long long *)nullptr, S);
-    else if (grad_p || !q.coef) hipLaunchKernelGGL(k_backward<false>, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid, grad_p, (unsigned long long *)nullptr, S);
-    else hipLaunchKernelGGL(k_backward_apply, grid, dim3(64), 0, st, G, c.pp, VB, q, ws.block_adj, grad_grid);     // (coefficients: dsdf_grad_sweep)
-    return check_launch("k_backward");
+    fill_views(c, 0, n_views, VB);
+    // (the non-direct integrators' coefficients: dsdf_grad_sweep -- unless dL/d(sdf.p) is wanted, which k_backward_apply does not give)
+    return backward_batch(c, ws, q, VB, n_views, film_total, grad_image, grad_grid, grad_p, nullptr, !c.direct && !grad_p && q.coef);
 }
 
 }  // extern "C"

@@ -337,7 +337,6 @@ class HipOps:
     # ---- one per-pixel proof for the sweep and the film of a window group (dsdf_share_pixel_skip, as dsdf.step_begin does)
     def begin_group(self, views):
         import torch
-        from . import _lib
         dev = self.grid.device
         n = len(views) * (self.W + 4) * (self.H + 4)
         self._group_views = list(views)
@@ -351,14 +350,10 @@ class HipOps:
         if bufs[gi] is None or bufs[gi].numel() < n:
             bufs[gi] = torch.empty(n, dtype=torch.uint8, device=dev)
         self._flags = bufs[gi]
-        self._share_lib = self.grid.lib(self.r._needs_extended(self.kw.get('shading')))
-        with torch.cuda.device(dev):
-            _lib.check(self._share_lib.dsdf_share_pixel_skip(self.r._ptr(self._flags), self._flags.numel()))
+        self._share_lib = self.r.share_proof_open(self.grid, self.kw.get('shading'), self._flags)
 
     def end_group(self):
-        import torch
-        with torch.cuda.device(self.grid.device):
-            self._share_lib.dsdf_share_pixel_skip(None, 0)
+        self.r.share_proof_close(self.grid, self._share_lib)
         self._flag_views = getattr(self, '_group_views', None)
 
     def row_costs(self):

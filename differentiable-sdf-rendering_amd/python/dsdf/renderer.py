@@ -7,6 +7,7 @@ primal image comes from an (seed, spp) render without gradients, the backward
 from an independent (seed_grad, spp_grad) re-render
 (python/integrators/reparam.py:187-190).
 """
+import contextlib
 import ctypes as C
 
 import os
@@ -45,6 +46,14 @@ def _stream():
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _floats(a):
+    return (C.c_float * len(a))(*[float(v) for v in a])
+
+
+def _as_list(sensors):
+    return list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
 
 
 def _require_dev(t, name, dtype=torch.float32):
@@ -110,8 +119,7 @@ class SdfGrid:
         inv = np.linalg.inv(tw)
         corners = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)])
         w = corners @ tw[:3, :3].T + tw[:3, 3]
-        f = lambda a: (C.c_float * len(a))(*[float(v) for v in a])
-        self.transform = (f(inv[:3, :].reshape(-1)), f(w.min(0)), f(w.max(0)))
+        self.transform = (_floats(inv[:3, :].reshape(-1)), _floats(w.min(0)), _floats(w.max(0)))
         return self
 
     _IDENTITY = None
@@ -126,8 +134,7 @@ class SdfGrid:
         tf = self.transform
         if tf is None:
             if SdfGrid._IDENTITY is None:
-                f = lambda a: (C.c_float * len(a))(*[float(v) for v in a])
-                SdfGrid._IDENTITY = (f([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]), f([0, 0, 0]), f([1, 1, 1]))
+                SdfGrid._IDENTITY = (_floats([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]), _floats([0, 0, 0]), _floats([1, 1, 1]))
             tf = SdfGrid._IDENTITY
         lib = _lib.load_xf()
         with torch.cuda.device(self.device):
@@ -280,15 +287,6 @@ class Shading:
         return st, keep
 
 
-def _shading_arg(integrator, shading, n_views, n_lanes, emitter_samples=None, grad_albedo=None, bsdf_samples=None):
-    if INTEGRATORS[integrator] != DSDF_DIRECT:
-        return None, None
-    if shading is None:
-        raise _lib.DsdfError("sdf_direct_reparam needs shading=dsdf.Shading(albedo, ...)")
-    st, keep = shading.to_struct(n_views, n_lanes, emitter_samples, grad_albedo, bsdf_samples)
-    return C.byref(st), (st, keep)
-
-
 def eval_cubic(grid, points, order=2):
     """A1. points (n,3) -> v (n,), g (n,3), H (n,6: xx,yy,zz,xy,xz,yz)."""
     lib = grid.lib()
@@ -354,7 +352,7 @@ def surface_interaction(grid, rays_o, rays_d, t):
 
 
 def _views(sensors):
-    sensors = list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
+    sensors = _as_list(sensors)
     W, H = sensors[0].film_size()
     for s in sensors:
         if s.film_size() != (W, H):
@@ -383,6 +381,53 @@ def _sampler_args(n_views, seeds, offsets, n_lanes):
     return None, cseeds
 
 
+class _Call:
+    """One render call as the library takes it: what the render entry points of include/dsdf.h share -- the library the grid's
+    calls go to, views, sampler, integrator, flags, shading -- checked and converted once."""
+
+    def __init__(self, grid, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SILHOUETTE, reparam=True, empty_space_skip=True,
+                 shading=None, emitter_samples=None, bsdf_samples=None, grad_albedo=None):
+        self.grid, self.params = grid, grid.params
+        self.extended = _needs_extended(shading)
+        self.lib = grid.lib(self.extended)
+        self.sensors, self.cams, self.W, self.H = _views(sensors)
+        self.nv, self.spp = len(self.sensors), int(spp)
+        self.n_lanes = (self.W + 4) * (self.H + 4) * self.spp
+        self.offsets, self.cseeds = _sampler_args(self.nv, seeds, offsets, self.n_lanes)
+        self.integrator = INTEGRATORS[integrator]
+        self.flags = (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip)
+        self.sh = self._keep = None
+        if self.integrator == DSDF_DIRECT:
+            if shading is None:
+                raise _lib.DsdfError("sdf_direct_reparam needs shading=dsdf.Shading(albedo, ...)")
+            st, keep = shading.to_struct(self.nv, self.n_lanes, emitter_samples, grad_albedo, bsdf_samples)
+            self.sh, self._keep = C.byref(st), (st, keep)      # (_keep: the struct and the tensors it points to, alive with this object)
+
+    def args(self):
+        """The leading arguments of every render entry point."""
+        g = self.grid
+        return (_ptr(g.padded), g.rx, g.ry, g.rz, C.byref(self.params), self.cams, self.nv, self.W, self.H, self.spp,
+                _ptr(self.offsets), self.cseeds, self.integrator, self.flags, self.sh)
+
+    def workspace(self, diff):
+        """The device's cached scratch buffer, sized for the views of one launch of a gradient pass (diff) or a primal one."""
+        size = self.lib.dsdf_render_workspace_size if diff else self.lib.dsdf_forward_workspace_size
+        extra = 0
+        if not diff and self.integrator == DSDF_DIRECT:
+            # room for the cell table of the shadow rays behind the workspace proper (include/dsdf.h: dsdf_cell_table_size)
+            extra = int(self.lib.dsdf_cell_table_size(self.grid.rx, self.grid.ry, self.grid.rz)) + 256
+        return _workspace(self.grid.device, size(self.W, self.H, self.spp, min(self.nv, MAX_VIEWS_PER_LAUNCH), self.integrator) + extra,
+                          size(self.W, self.H, self.spp, 1, self.integrator))
+
+    def image(self, wanted=True):
+        return torch.empty(self.nv, self.H, self.W, 3, dtype=torch.float32, device=self.grid.device) if wanted else None
+
+    def run(self, entry, *tail):
+        """lib.<entry>(the shared arguments, *tail, stream) on the grid's device."""
+        with torch.cuda.device(self.grid.device):
+            _lib.check(getattr(self.lib, entry)(*self.args(), *tail, _stream()))
+
+
 def sampler_offsets(sensors, spp, seeds, mirror=False, device=None):
     """`sampler.next_2d()` of the built-in `independent` sampler for every lane of every view -> (n_views, (W+4)(H+4)spp, 2); mirror:
     1 - r, the film offsets of the antithetic pair (python/integrators/reparam.py:167-178; dsdf_sampler_2d)."""
@@ -402,24 +447,10 @@ def render_forward(grid, sensors, spp, seeds=None, offsets=None, integrator=DSDF
                    empty_space_skip=True, shading=None, emitter_samples=None, bsdf_samples=None):
     """`ReparamIntegrator.render` for a batch of views -> (n_views, H, W, 3).  `shading` (dsdf.Shading) and the
     optional per-lane `emitter_samples` belong to sdf_direct_reparam."""
-    lib = grid.lib(_needs_extended(shading))
-    sensors, cams, W, H = _views(sensors)
-    nv = len(sensors)
-    n_lanes = (W + 4) * (H + 4) * int(spp)
-    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
-    dev = grid.device
-    img = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev)
-    # (sdf_direct_reparam: room for the cell table of the shadow rays behind the workspace proper, include/dsdf.h dsdf_cell_table_size)
-    extra = (int(lib.dsdf_cell_table_size(grid.rx, grid.ry, grid.rz)) + 256) if INTEGRATORS[integrator] == DSDF_DIRECT else 0
-    wsb = lib.dsdf_forward_workspace_size(W, H, int(spp), min(nv, MAX_VIEWS_PER_LAUNCH), INTEGRATORS[integrator]) + extra
-    ws = _workspace(dev, wsb, lib.dsdf_forward_workspace_size(W, H, int(spp), 1, INTEGRATORS[integrator]))
-    wsb = ws.numel()
-    sh, _keep = _shading_arg(integrator, shading, nv, n_lanes, emitter_samples, bsdf_samples=bsdf_samples)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_render_forward(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, C.byref(grid.params), cams, nv,
-                                           W, H, int(spp), _ptr(offsets), cseeds, INTEGRATORS[integrator],
-                                           (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip),
-                                           sh, _ptr(img), _ptr(ws), wsb, _ptr(stats), _stream()))
+    c = _Call(grid, sensors, spp, seeds, offsets, integrator, reparam, empty_space_skip, shading, emitter_samples, bsdf_samples)
+    img = c.image()
+    ws = c.workspace(False)
+    c.run('dsdf_render_forward', _ptr(img), _ptr(ws), ws.numel(), _ptr(stats))
     return img
 
 
@@ -430,17 +461,13 @@ def render_aovs(grid, sensors, spp, seeds=None, offsets=None):
     """The debug channels of `use_aovs` + `WarpField2D.return_aovs` (python/integrators/reparam.py:160-165, 263-267) for a batch of
     views -> (n_views, H, W, 11) in the order of AOV_NAMES.  The reference writes two of them, the loop state of the primary
     ray's differentiable trace (`i`, `weight_sum`: python/shapes.py:240-242; dsdf_render_aovs); the other nine are zero there too."""
-    lib = grid.lib()
-    sensors, cams, W, H = _views(sensors)
-    nv = len(sensors)
-    n_lanes = (W + 4) * (H + 4) * int(spp)
-    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
-    dev = grid.device
+    c = _Call(grid, sensors, spp, seeds, offsets)
+    lib, nv, W, H, dev = c.lib, c.nv, c.W, c.H, grid.device
     two = torch.empty(nv, H, W, 2, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.dsdf_aov_workspace_size(W, H, min(nv, MAX_VIEWS_PER_LAUNCH)), lib.dsdf_aov_workspace_size(W, H, 1))
     with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_render_aovs(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, C.byref(grid.params), cams, nv, W, H, int(spp),
-                                        _ptr(offsets), cseeds, _ptr(two), _ptr(ws), ws.numel(), _stream()))
+        # (the AOV pass takes the call up to its sampler: no integrator, flags or shading)
+        _lib.check(lib.dsdf_render_aovs(*c.args()[:12], _ptr(two), _ptr(ws), ws.numel(), _stream()))
     out = torch.zeros(nv, H, W, len(AOV_NAMES), dtype=torch.float32, device=dev)
     out[..., AOV_NAMES.index('i')] = two[..., 0]
     out[..., AOV_NAMES.index('weight_sum')] = two[..., 1]
@@ -453,12 +480,8 @@ def render_backward(grid, sensors, spp, grad_image, grad_grid=None, seeds=None, 
     """`ReparamIntegrator.render_backward`: accumulates dL/dsdf into grad_grid (Z,Y,X) and, if given,
     dL/d(sdf.p) into grad_p (3 floats on the device; `sdf.p`, python/shapes.py:471) and, for
     sdf_direct_reparam, dL/d(albedo) into grad_albedo (shaped like shading.albedo)."""
-    lib = grid.lib(_needs_extended(shading))
-    sensors, cams, W, H = _views(sensors)
-    nv = len(sensors)
-    n_lanes = (W + 4) * (H + 4) * int(spp)
-    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
-    dev = grid.device
+    c = _Call(grid, sensors, spp, seeds, offsets, integrator, reparam, empty_space_skip, shading, emitter_samples, bsdf_samples, grad_albedo)
+    nv, W, H, dev = c.nv, c.W, c.H, grid.device
     grad_image = _require_dev(grad_image, 'grad_image')
     if grad_image.numel() != nv * H * W * 3:
         raise _lib.DsdfError(f"grad_image must be (n_views,H,W,3) = {(nv, H, W, 3)}, got {tuple(grad_image.shape)}")
@@ -472,17 +495,9 @@ def render_backward(grid, sensors, spp, grad_image, grad_grid=None, seeds=None, 
         if grad_p.numel() != 3 or grad_p.dtype != torch.float32 or not grad_p.is_contiguous():
             raise _lib.DsdfError("grad_p must be a contiguous float32 tensor of 3 elements")
         _require_dev(grad_p, 'grad_p')
-    img = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev) if return_image else None
-    wsb = lib.dsdf_render_workspace_size(W, H, int(spp), min(nv, MAX_VIEWS_PER_LAUNCH), INTEGRATORS[integrator])
-    ws = _workspace(dev, wsb, lib.dsdf_render_workspace_size(W, H, int(spp), 1, INTEGRATORS[integrator]))
-    wsb = ws.numel()
-    sh, _keep = _shading_arg(integrator, shading, nv, n_lanes, emitter_samples, grad_albedo, bsdf_samples)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_render_backward(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, C.byref(grid.params), cams, nv,
-                                            W, H, int(spp), _ptr(offsets), cseeds, INTEGRATORS[integrator],
-                                            (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip),
-                                            sh, _ptr(grad_image), _ptr(grad_grid), _ptr(grad_p),
-                                            _ptr(img), _ptr(ws), wsb, _ptr(stats), _stream()))
+    img = c.image(return_image)
+    ws = c.workspace(True)
+    c.run('dsdf_render_backward', _ptr(grad_image), _ptr(grad_grid), _ptr(grad_p), _ptr(img), _ptr(ws), ws.numel(), _ptr(stats))
     return (grad_grid, img) if return_image else grad_grid
 
 
@@ -491,12 +506,7 @@ def render_forward_grad(grid, sensors, spp, tangent_data=None, tangent_p=None, s
                         emitter_samples=None, bsdf_samples=None):
     """`ReparamIntegrator.render_forward` (python/integrators/reparam.py:192-196): forward-mode gradient image(s)
     (n_views,H,W,3) for a tangent on sdf.data (tensor shaped like the grid) and / or on sdf.p (3 floats)."""
-    lib = grid.lib(_needs_extended(shading))
-    sensors, cams, W, H = _views(sensors)
-    nv = len(sensors)
-    n_lanes = (W + 4) * (H + 4) * int(spp)
-    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
-    dev = grid.device
+    c = _Call(grid, sensors, spp, seeds, offsets, integrator, reparam, empty_space_skip, shading, emitter_samples, bsdf_samples)
     tpad = None
     if tangent_data is not None:
         t = tangent_data[..., 0] if tangent_data.dim() == 4 else tangent_data
@@ -509,17 +519,9 @@ def render_forward_grad(grid, sensors, spp, tangent_data=None, tangent_p=None, s
         tp = (C.c_float * 3)(*[float(v) for v in vals])
     if tpad is None and tp is None:
         raise _lib.DsdfError("render_forward_grad needs tangent_data and / or tangent_p")
-    out = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev)
-    img = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev) if return_image else None
-    wsb = lib.dsdf_render_workspace_size(W, H, int(spp), min(nv, MAX_VIEWS_PER_LAUNCH), INTEGRATORS[integrator])
-    ws = _workspace(dev, wsb, lib.dsdf_render_workspace_size(W, H, int(spp), 1, INTEGRATORS[integrator]))
-    wsb = ws.numel()
-    sh, _keep = _shading_arg(integrator, shading, nv, n_lanes, emitter_samples, bsdf_samples=bsdf_samples)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_render_forward_grad(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, C.byref(grid.params), cams, nv,
-                                                W, H, int(spp), _ptr(offsets), cseeds, INTEGRATORS[integrator],
-                                                (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip), sh,
-                                                _ptr(tpad), tp, _ptr(out), _ptr(img), _ptr(ws), wsb, _stream()))
+    out, img = c.image(), c.image(return_image)
+    ws = c.workspace(True)
+    c.run('dsdf_render_forward_grad', _ptr(tpad), tp, _ptr(out), _ptr(img), _ptr(ws), ws.numel())
     return (out, img) if return_image else out
 
 
@@ -536,23 +538,10 @@ def new_film(n_views, W, H, integrator, device):
 def render_film(grid, sensors, spp, film, rows, seeds=None, offsets=None, integrator=DSDF_SILHOUETTE, reparam=True,
                 empty_space_skip=True, shading=None, emitter_samples=None, stats=None):
     """Primal samples of the film-block rows [rows[0], rows[1]) of every view, ACCUMULATED into `film`."""
-    lib = grid.lib(_needs_extended(shading))
-    sensors, cams, W, H = _views(sensors)
-    nv = len(sensors)
-    n_lanes = (W + 4) * (H + 4) * int(spp)
-    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
-    dev = grid.device
+    c = _Call(grid, sensors, spp, seeds, offsets, integrator, reparam, empty_space_skip, shading, emitter_samples)
     _require_dev(film, 'film')
-    # (sdf_direct_reparam: room for the cell table of the shadow rays behind the workspace proper, include/dsdf.h dsdf_cell_table_size)
-    extra = (int(lib.dsdf_cell_table_size(grid.rx, grid.ry, grid.rz)) + 256) if INTEGRATORS[integrator] == DSDF_DIRECT else 0
-    wsb = lib.dsdf_forward_workspace_size(W, H, int(spp), min(nv, MAX_VIEWS_PER_LAUNCH), INTEGRATORS[integrator]) + extra
-    ws = _workspace(dev, wsb, lib.dsdf_forward_workspace_size(W, H, int(spp), 1, INTEGRATORS[integrator]))
-    sh, _keep = _shading_arg(integrator, shading, nv, n_lanes, emitter_samples)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_render_film(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, C.byref(grid.params), cams, nv, W, H, int(spp),
-                                        _ptr(offsets), cseeds, INTEGRATORS[integrator],
-                                        (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip), sh,
-                                        int(rows[0]), int(rows[1]), _ptr(film), _ptr(ws), ws.numel(), _ptr(stats), _stream()))
+    ws = c.workspace(False)
+    c.run('dsdf_render_film', int(rows[0]), int(rows[1]), _ptr(film), _ptr(ws), ws.numel(), _ptr(stats))
     return film
 
 
@@ -577,29 +566,19 @@ class GradSweep:
     sensors of a config) are handled as consecutive parts of at most that many views, each with its own queue."""
 
     def __new__(cls, grid, sensors, *a, **kw):
-        sensors = list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
-        if len(sensors) > MAX_VIEWS_PER_LAUNCH and cls is GradSweep:
+        if len(_as_list(sensors)) > MAX_VIEWS_PER_LAUNCH and cls is GradSweep:
             return object.__new__(_GradSweepParts)
         return object.__new__(cls)
 
     def __init__(self, grid, sensors, spp, rows, seeds=None, offsets=None, integrator=DSDF_SILHOUETTE, reparam=True,
                  empty_space_skip=True, shading=None, emitter_samples=None, grad_albedo=None, workspace=None):
-        self.extended = _needs_extended(shading)
-        self.lib = grid.lib(self.extended)
-        self.grid = grid
+        c = self.call = _Call(grid, sensors, spp, seeds, offsets, integrator, reparam, empty_space_skip, shading, emitter_samples,
+                              grad_albedo=grad_albedo)
         # the parameter block as it is NOW (sdf.p, warp settings): backward() may run after the caller touched grid.params
-        self.params = type(grid.params).from_buffer_copy(grid.params)
-        self.sensors, self.cams, self.W, self.H = _views(sensors)
-        self.nv = len(self.sensors)
-        self.spp = int(spp)
-        n_lanes = (self.W + 4) * (self.H + 4) * self.spp
-        self.offsets, self.cseeds = _sampler_args(self.nv, seeds, offsets, n_lanes)
-        self.integrator = INTEGRATORS[integrator]
-        self.flags = (DSDF_REPARAM if reparam else 0) | _proof_flags(empty_space_skip)
+        c.params = type(grid.params).from_buffer_copy(grid.params)
+        self.grid, self.nv = grid, c.nv
         self.rows = (int(rows[0]), int(rows[1]))
-        self.sh, self._keep = _shading_arg(integrator, shading, self.nv, n_lanes, emitter_samples, grad_albedo)
-        wsb = int(self.lib.dsdf_render_workspace_size(self.W, self.H, self.spp, self.nv, self.integrator))
-        self.ws_bytes = wsb
+        wsb = self.ws_bytes = int(c.lib.dsdf_render_workspace_size(c.W, c.H, c.spp, c.nv, c.integrator))
         self.grid_version = None                              # set by sweep(): the grid the queue in `ws` belongs to
         # the backward queue lives in this buffer between the two halves: private to the sweep unless the caller lends one
         if workspace is not None and workspace.numel() >= wsb:
@@ -607,17 +586,15 @@ class GradSweep:
         else:
             self.ws = torch.empty(wsb, dtype=torch.uint8, device=grid.device)
 
-    def _args(self):
-        g = self.grid
-        return (_ptr(g.padded), g.rx, g.ry, g.rz, C.byref(self.params), self.cams, self.nv, self.W, self.H, self.spp,
-                _ptr(self.offsets), self.cseeds, self.integrator, self.flags, self.sh)
+    def _run(self, entry, *tail):
+        c = self.call
+        c.lib = self.grid.lib(c.extended)                     # (re-applies a general transform: state of the library instance)
+        c.run(entry, *tail, _ptr(self.ws), self.ws.numel())
 
     def sweep(self, film):
         _require_dev(film, 'film')
-        self.lib = self.grid.lib(self.extended)               # (re-applies a general transform: state of the library instance)
         self.grid_version = self.grid.version
-        with torch.cuda.device(self.grid.device):
-            _lib.check(self.lib.dsdf_grad_sweep(*self._args(), self.rows[0], self.rows[1], _ptr(film), _ptr(self.ws), self.ws.numel(), _stream()))
+        self._run('dsdf_grad_sweep', self.rows[0], self.rows[1], _ptr(film))
         return film
 
     def make_private(self):
@@ -626,17 +603,15 @@ class GradSweep:
 
     def backward(self, film_total, grad_image, grad_grid, grad_p=None):
         _require_dev(film_total, 'film_total'); grad_image = _require_dev(grad_image, 'grad_image'); _require_dev(grad_grid, 'grad_grid')
-        if grad_image.numel() != self.nv * self.H * self.W * 3:
-            raise _lib.DsdfError(f"grad_image must be (n_views,H,W,3) = {(self.nv, self.H, self.W, 3)}, got {tuple(grad_image.shape)}")
+        c = self.call
+        if grad_image.numel() != c.nv * c.H * c.W * 3:
+            raise _lib.DsdfError(f"grad_image must be (n_views,H,W,3) = {(c.nv, c.H, c.W, 3)}, got {tuple(grad_image.shape)}")
         if self.grid_version != self.grid.version:
             # the padded buffer is rewritten in place by SdfGrid.update: the queued samples (warp points, records) belong to the
             # grid that was traced, the lookups of the backward would read the new one
             raise _lib.DsdfError("the grid was updated (SdfGrid.update / set_data) between the gradient sweep of this step and its "
                                  "backward: back-propagate before the optimiser step, or render again")
-        self.lib = self.grid.lib(self.extended)
-        with torch.cuda.device(self.grid.device):
-            _lib.check(self.lib.dsdf_grad_backward(*self._args(), _ptr(film_total), _ptr(grad_image), _ptr(grad_grid), _ptr(grad_p),
-                                                   _ptr(self.ws), self.ws.numel(), _stream()))
+        self._run('dsdf_grad_backward', _ptr(film_total), _ptr(grad_image), _ptr(grad_grid), _ptr(grad_p))
         return grad_grid
 
     def record_stream(self, stream):
@@ -691,6 +666,31 @@ class StepHandle:
         self.done = False
 
 
+def share_proof_open(grid, shading, flags):
+    """Opens the bracket in which the render calls of this thread that see the same grid, sensors and film size share ONE per-pixel
+    proof (include/dsdf.h: dsdf_share_pixel_skip): the first computes the flags into `flags` (uint8, one per film-block pixel and
+    view), the others wait for it and read them.  Returns the library the bracket is open on, for share_proof_close."""
+    lib = grid.lib(_needs_extended(shading))
+    with torch.cuda.device(grid.device):
+        _lib.check(lib.dsdf_share_pixel_skip(_ptr(flags), flags.numel()))
+    return lib
+
+
+def share_proof_close(grid, lib):
+    with torch.cuda.device(grid.device):
+        lib.dsdf_share_pixel_skip(None, 0)
+
+
+@contextlib.contextmanager
+def shared_proof(grid, shading, flags):
+    """The bracket of share_proof_open / share_proof_close around a block of render calls."""
+    lib = share_proof_open(grid, shading, flags)
+    try:
+        yield
+    finally:
+        share_proof_close(grid, lib)
+
+
 def _lease_sweep_workspace(dev):
     """The cached sweep workspace of `dev` unless a step that has begun and not yet finished still owns its queue."""
     ent = _sweep_workspaces.get(dev)
@@ -708,7 +708,7 @@ def step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator=DSDF_
     beside the primal render; both passes share one empty-space / hit proof (dsdf_share_pixel_skip).  step_finish(handle,
     grad_image, ...) then runs what is left of the backward (dsdf_grad_backward).  This is the autograd boundary of the render
     op: torch's forward() calls step_begin, backward() calls step_finish."""
-    sensors = list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
+    sensors = _as_list(sensors)
     W, H = sensors[0].film_size()
     dev = grid.device
     main = torch.cuda.current_stream(dev)
@@ -719,28 +719,24 @@ def step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator=DSDF_
         side = _side_streams[dev] = torch.cuda.Stream(dev, priority=-1)
     side.wait_stream(main)                                    # the grid (and whatever produced it) is ready
     # one per-pixel proof for both passes (dsdf_share_pixel_skip): the sweep writes the flags, the primal render reads them
-    lib = grid.lib(_needs_extended(shading))
     nflag = len(sensors) * (W + 4) * (H + 4)
     flags = _skip_buffers.get(dev)
     if flags is None or flags.numel() < nflag:
         flags = _skip_buffers[dev] = torch.empty(nflag, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        if os.environ.get('DSDF_SHARE_SKIP', '1') != '0':          # (A/B switch, tools/ab_step.py)
-            _lib.check(lib.dsdf_share_pixel_skip(_ptr(flags), flags.numel()))
-        try:
-            ws, lease = _lease_sweep_workspace(dev)
-            with torch.cuda.stream(side):
-                sweep = GradSweep(grid, sensors, spp_grad, (0, H + 4), seeds=seeds_grad, integrator=integrator, reparam=reparam,
-                                  shading=shading, grad_albedo=grad_albedo, workspace=ws)
-                if sweep.ws is not None and sweep.ws is not ws:
-                    if lease is not None:
-                        lease['leased'] = False
-                    # (a larger / first buffer: it becomes the cached one, owned by this step until step_finish)
-                    lease = _sweep_workspaces[dev] = {'ws': sweep.ws, 'leased': True}
-                film_g = sweep.sweep(new_film(len(sensors), W, H, integrator, dev))
-            img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading)
-        finally:
-            lib.dsdf_share_pixel_skip(None, 0)
+    # (DSDF_SHARE_SKIP=0, INTEGRATION.md: a proof per pass -- the tests compare the shared flags with that path)
+    share = os.environ.get('DSDF_SHARE_SKIP', '1') != '0'
+    with torch.cuda.device(dev), (shared_proof(grid, shading, flags) if share else contextlib.nullcontext()):
+        ws, lease = _lease_sweep_workspace(dev)
+        with torch.cuda.stream(side):
+            sweep = GradSweep(grid, sensors, spp_grad, (0, H + 4), seeds=seeds_grad, integrator=integrator, reparam=reparam,
+                              shading=shading, grad_albedo=grad_albedo, workspace=ws)
+            if sweep.ws is not None and sweep.ws is not ws:
+                if lease is not None:
+                    lease['leased'] = False
+                # (a larger / first buffer: it becomes the cached one, owned by this step until step_finish)
+                lease = _sweep_workspaces[dev] = {'ws': sweep.ws, 'leased': True}
+            film_g = sweep.sweep(new_film(len(sensors), W, H, integrator, dev))
+        img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading)
     return img, StepHandle(sweep, film_g, main, side, lease)
 
 
@@ -773,7 +769,7 @@ def render_step(grid, sensors, spp, spp_grad, loss_grad, grad_grid, seeds, seeds
     gradient `loss_grad(images)`, gradient pass at `spp_grad` accumulating into `grad_grid` -- the same three library calls as
     render_forward + render_backward, scheduled on TWO HIP streams (step_begin / step_finish): only the backward proper
     (dsdf_grad_backward) waits for both the primal image and the sweep.  Returns the images."""
-    sensors = list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
+    sensors = _as_list(sensors)
     if not overlap:
         img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading)
         render_backward(grid, sensors, spp_grad, loss_grad(img), grad_grid=grad_grid, seeds=seeds_grad, integrator=integrator,
@@ -957,7 +953,7 @@ def render(data, grid, sensors, spp, seed=0, spp_grad=None, seed_grad=0, integra
     """Differentiable render of `data` (the tensor behind `grid`) for one or more
     sensors: returns (n_views,H,W,3) attached to `data` and, if given, to the
     translation `p` (3,) (`SamplingIntegrator.sdf.p`)."""
-    sensors = list(sensors) if isinstance(sensors, (list, tuple)) else [sensors]
+    sensors = _as_list(sensors)
     albedo = shading.albedo if shading is not None else None      # attached when it requires grad (sdf_direct_reparam)
     rough = shading.roughness if shading is not None else None    # ... and the principled roughness volume
     attached = any(isinstance(t, torch.Tensor) and t.requires_grad for t in (data, p, albedo, rough))

@@ -64,6 +64,38 @@ def test_argument_validation_before_device_work(built):
     assert rc == -1 and b'wavefront' in lib.dsdf_last_error()       # reparam.py:48-50
     rc = lib.dsdf_render_forward(one, 4, 4, 4, C.byref(p), cam, 1, 8, 8, 4, None, None, 2, 1, None, one, one, 1 << 30, None, None)
     assert rc == -1 and b'dsdf_shading' in lib.dsdf_last_error()     # sdf_direct_reparam without its scene inputs
+    # every render entry point: what it refuses on top of the shared checks, with its own name in the text.  8x8 film, spp 4, a 4^3 grid;
+    # `one` stands for every non-null pointer
+    seeds = (C.c_uint32 * 1)(1)
+    big = 1 << 30
+    cam2 = (dsdf.DsdfCamera * 2)()
+    one_view = lib.dsdf_render_workspace_size(8, 8, 4, 1, 0)
+
+    def call(fn, *tail, cams=cam, nv=1, sd=seeds):
+        return (getattr(lib, fn), (one, 4, 4, 4, C.byref(p), cams, nv, 8, 8, 4, None, sd, 0, 1, None) + tail)
+
+    cases = [
+        (call('dsdf_render_forward', None, one, big, None, None), -1, b'dsdf_render_forward: image_out is null'),
+        (call('dsdf_render_forward', one, one, big, None, None, sd=None), -1, b'dsdf_render_forward: need offsets or seeds'),
+        (call('dsdf_render_backward', None, one, None, None, one, big, None, None), -1, b'dsdf_render_backward: null gradient buffer'),
+        (call('dsdf_render_backward', one, one, None, None, one, big, None, None, sd=None), -1, b'dsdf_render_backward: need offsets or seeds'),
+        (call('dsdf_render_backward', one, one, None, None, one, 16, None, None), -2, b'workspace too small'),
+        (call('dsdf_render_forward_grad', one, None, None, None, one, big, None), -1, b'grad_image_out is null'),
+        (call('dsdf_render_forward_grad', None, None, one, None, one, big, None), -1, b'need a tangent'),
+        (call('dsdf_render_film', 5, 5, one, one, big, None, None), -1, b'bad film-block row window'),
+        (call('dsdf_render_film', 0, 12, None, one, big, None, None), -1, b'dsdf_render_film: film is null'),
+        (call('dsdf_grad_sweep', 0, 13, one, one, big, None), -1, b'bad film-block row window'),
+        (call('dsdf_grad_sweep', 0, 12, None, one, big, None), -1, b'dsdf_grad_sweep: film is null'),
+        (call('dsdf_grad_sweep', 0, 12, one, one, one_view, None, cams=cam2, nv=2, sd=(C.c_uint32 * 2)(1, 2)), -2, b'must hold all views'),
+        (call('dsdf_grad_backward', None, one, one, None, one, big, None), -1, b'dsdf_grad_backward: null buffer'),
+        (call('dsdf_grad_backward', one, one, one, None, one, one_view, None, cams=cam2, nv=2), -2, b'the one dsdf_grad_sweep filled'),
+    ]
+    for (fn, args), want, text in cases:
+        rc = fn(*args)
+        assert rc == want and text in lib.dsdf_last_error(), (fn.__name__, rc, lib.dsdf_last_error())
+    aov = lambda out, wsb: lib.dsdf_render_aovs(one, 4, 4, 4, C.byref(p), cam, 1, 8, 8, 4, None, seeds, out, one, wsb, None)
+    assert aov(None, big) == -1 and b'dsdf_render_aovs: null pointer argument' in lib.dsdf_last_error()
+    assert aov(one, 16) == -2 and b'dsdf_aov_workspace_size' in lib.dsdf_last_error()
 
 
 def test_product_refuses_cpu_tensors(built):
