@@ -18,14 +18,11 @@
     // tools/probe/hwid_probe.hip; a performance assumption only).  The ~1024 resident waves of an XCD therefore work on ONE
     // tile at a time and its 4 MiB L2 holds that tile's part of the grid.  Within a share the items go out in order through 8
     // counters (counter `sub` hands out the share's items sub, sub + 8, ...; the first gridDim.x / 64 of each are
-    // pre-assigned).  A worker whose share is exhausted moves on to the next XCD's.
+    // pre-assigned).  A worker whose share is exhausted moves on to the next XCD's.  (k_direct_items walks the list in the same way.)
     const uint32_t sub = (blockIdx.x >> 3) & 7u, first = gridDim.x / DSDF_TICKETS;
     uint32_t share = blockIdx.x & 7u, hops = 0;
     const uint32_t my_subq = tail_subq();        // tail hand-off queue of this worker: (the XCD it runs on, its ticket counter)
-    auto item_of = [&](uint32_t sh, uint32_t j) { return ((j / DSDF_ITEM_SEG) * 8u + sh) * DSDF_ITEM_SEG + j % DSDF_ITEM_SEG; };
-    auto draw = [&](uint32_t sh) {            // lane 0: the next item of share sh (one round trip ahead of its use)
-        return item_of(sh, sub + 8u * (first + atomicAdd(items + 16 + 16 * (sh * 8u + sub), 1u)));
-    };
+    auto draw = [&](uint32_t sh) { return ticket_draw(items, sh, sub, first); };    // lane 0: the next item of share sh (one round trip ahead of its use)
     uint32_t item = item_of(share, blockIdx.x >> 3), next = 0;
     if (lid == 0) next = draw(share);
     while (true) {
@@ -50,6 +47,8 @@
         const bool known_hit = !DIFF && !DIRECT && (proof & DSDF_PX_HIT) && A.integrator == DSDF_SILHOUETTE;
         const uint32_t unit = pix * chunks + item % chunks;
         const uint32_t lane = unit * 64u + (uint32_t)lid;
+        // where the rays this wave does not finish go (HandOff / PlainHandOff, dsdf_tail.h)
+        auto hand_off = [&tq, my_subq, item, view, lane](auto &ho) { ho.tq = tq; ho.sub = tq.per_xcd ? my_subq : item % DSDF_TAIL_SUBQ; ho.view = view; ho.lane = lane; };
         TraceOut tr, trs, trb;
         clear_trace(tr);
         int lit = 0;
@@ -71,7 +70,7 @@
                     DirectFetch F;
                     if (tq.state) {
                         HandOff ho;
-                        ho.tq = tq; ho.sub = tq.per_xcd ? my_subq : item % DSDF_TAIL_SUBQ; ho.view = view; ho.lane = lane;
+                        hand_off(ho);
                         trace_diff(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F, ho);
                     } else trace_diff(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F);
                     const Queue qv = view_queue(qall, view);
@@ -80,10 +79,10 @@
                     WaveCellCache F; F.taps = wave_lds; F.lid = lid;
                     if (tq.state) {
                         PlainHandOff ho;
-                        ho.tq = tq; ho.sub = tq.per_xcd ? my_subq : item % DSDF_TAIL_SUBQ; ho.view = view; ho.lane = lane;
+                        hand_off(ho);
                         trace_plain(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F, ho);
                     } else trace_plain(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F);
-                    hit_t[(size_t)view * ((size_t)npix * (uint32_t)A.spp) + lane] = tr.its_t;
+                    hit_t[hit_slot(npix, A.spp, view, lane)] = tr.its_t;
                 }
             }
         } else if (proven) {
@@ -102,14 +101,14 @@
                 DirectFetch F;
                 if (!DIRECT && tq.state) {
                     HandOff ho;
-                    ho.tq = tq; ho.sub = tq.per_xcd ? my_subq : item % DSDF_TAIL_SUBQ; ho.view = view; ho.lane = lane;
+                    hand_off(ho);
                     trace_diff(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F, ho);
                 } else trace_diff(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F);
             } else {
                 WaveCellCache F; F.taps = wave_lds; F.lid = lid;
                 if (!DIRECT && tq.state) {
                     PlainHandOff ho;
-                    ho.tq = tq; ho.sub = tq.per_xcd ? my_subq : item % DSDF_TAIL_SUBQ; ho.view = view; ho.lane = lane;
+                    hand_off(ho);
                     trace_plain(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F, ho);
                 } else trace_plain(G, P, L.ray.o, L.ray.d, L.ray.maxt, tr, F);
             }
@@ -132,9 +131,7 @@
         if (!STORE_T) film_flush_wave<NCH>(block, A, px, py, lid, acc);
         bool need = false;
         if (DIFF && !STORE_T) {
-            const bool hit = tr.its_t < INFINITY;
-            const bool warp_cand = (A.flags & DSDF_REPARAM) && warp_weight_positive(G, P, L.ray.o, L.ray.d, tr);
-            need = warp_cand || (DIRECT ? lit != 0 : (hit && A.integrator == DSDF_SIMPLE_SHADING));
+            need = needs_backward<DIRECT>(G, P, A, L, tr, lit);
             queue_unit(view_queue(qall, view), unit, lane, need, lid, tr, DIRECT ? &trs : nullptr, (DIRECT && S.use_mis) ? &trb : nullptr);
         }
         if (STATS) add_stats(wst, tr, true, need);

@@ -207,6 +207,10 @@ __device__ __forceinline__ Queue view_queue(Queue q, uint32_t view) {
     if (q.coef) q.coef += (size_t)view * q.cap * q.coef_rows;
     return q;
 }
+// hit_t[view][npix * spp] of the wavefront sdf_direct_reparam (a sample's hit distance; its sign: the shadow ray was occluded): slot of a sample
+__device__ __forceinline__ size_t hit_slot(size_t npix, int spp, uint32_t view, uint32_t lane) {
+    return (size_t)view * (npix * (uint32_t)spp) + lane;
+}
 
 __device__ __forceinline__ void store_record(float *r, size_t c, const TraceOut &tr) {
     r[0] = tr.its_t; r[c] = tr.warp_t;
@@ -306,10 +310,12 @@ __device__ __forceinline__ void queue_unit(const Queue &q, uint32_t unit, uint32
 // ~8 ns).  Header of the list: [0] = number of listed pixels, then the counters (16 words apart).
 #define DSDF_TICKETS 64
 #define DSDF_ITEM_HDR (16 + 16 * DSDF_TICKETS)
-#ifndef DSDF_ITEM_SEG
-#define DSDF_ITEM_SEG 1024u         /* items per segment = the resident waves of an XCD; the list is tile-major with 1024-chunk tiles
-                                       (measured: 28.9 / 28.7 / 28.6 / 28.5 ms at 256 / 512 / 1024 / 4096) */
-#endif
+// (DSDF_ITEM_SEG, the items per segment of the list, and item_of: dsdf_lane.h)
+// Lane 0 of a worker draws the next item of share sh from ticket counter `sub` of that share: counter `sub` hands out the share's items
+// sub, sub + 8, ... (item_of), of which the first `first` = gridDim.x / DSDF_TICKETS are pre-assigned to the workers by block index.
+__device__ __forceinline__ uint32_t ticket_draw(uint32_t *items, uint32_t sh, uint32_t sub, uint32_t first) {
+    return item_of(sh, sub + 8u * (first + atomicAdd(items + 16 + 16 * (sh * 8u + sub), 1u)));
+}
 struct ItemOrder { int tw_log2, th_log2; uint32_t tiles_x, per_view; };    // candidate index -> pixel: tile-major within a view
 
 __global__ __launch_bounds__(256) void k_build_items(ViewBatch VB, int view0, int nv, const unsigned char *__restrict__ skip, unsigned far_bit,
@@ -415,8 +421,7 @@ __global__ __launch_bounds__(64) void k_direct_items(GridView G, dsdf_params P, 
     const uint32_t sub = (blockIdx.x >> 3) & 7u, first = gridDim.x / DSDF_TICKETS;
     uint32_t share = blockIdx.x & 7u, hops = 0;
     const uint32_t my_subq = tail_subq();
-    auto item_of = [&](uint32_t sh, uint32_t j) { return ((j / DSDF_ITEM_SEG) * 8u + sh) * DSDF_ITEM_SEG + j % DSDF_ITEM_SEG; };
-    auto draw = [&](uint32_t sh) { return item_of(sh, sub + 8u * (first + atomicAdd(items + 16 + 16 * (sh * 8u + sub), 1u))); };
+    auto draw = [&](uint32_t sh) { return ticket_draw(items, sh, sub, first); };    // (the ticket walk of dsdf_items_body.h)
     uint32_t item = item_of(share, blockIdx.x >> 3), next = 0;
     if (lid == 0) next = draw(share);
     while (true) {
@@ -443,7 +448,7 @@ __global__ __launch_bounds__(64) void k_direct_items(GridView G, dsdf_params P, 
             const uint32_t lane = unit * 64u + (uint32_t)lid;
             const Queue qv = view_queue(qall, view);
             // the primary ray's hit distance: hit_t (primal; its sign = the shadow ray was occluded) / row 0 of the sample's record (sweep)
-            const float ht = skip_trace ? INFINITY : (DIFF ? qv.rec[lane] : hit_t[(size_t)view * ((size_t)npix * (uint32_t)A.spp) + lane]);
+            const float ht = skip_trace ? INFINITY : (DIFF ? qv.rec[lane] : hit_t[hit_slot(npix, A.spp, view, lane)]);
             const bool occluded = !DIFF && (__float_as_uint(ht) >> 31) != 0u;
             const float its_t = DIFF ? ht : fabsf(ht);
             if (PHASE == 0) {
@@ -504,8 +509,7 @@ __global__ __launch_bounds__(64) void k_direct_items(GridView G, dsdf_params P, 
                     }
                 }
                 film_accum_wave<NCH>(px, py, rp.u, rp.v, rgb, wave_lds, lid, acc);
-                const bool warp_cand = (A.flags & DSDF_REPARAM) && warp_weight_positive(G, P, L.ray.o, L.ray.d, tr);
-                queue_unit(qv, unit, lane, warp_cand || lit != 0, lid, tr, &trs, nullptr);
+                queue_unit(qv, unit, lane, needs_backward<true>(G, P, A, L, tr, lit), lid, tr, &trs, nullptr);
             }
           }
             if (PHASE == 1) film_flush_wave<NCH>(blocks + (size_t)view * NCH * npix, A, px, py, lid, acc);
@@ -624,9 +628,7 @@ __global__ __launch_bounds__(DSDF_BLOCK) void k_render_pass(GridView G, dsdf_par
     if (windowed) tile_window_flush<NCH>(TW, block, A.Wb, A.Hb, lid);
     bool need = false;
     if (DIFF) {
-        const bool hit = tr.its_t < INFINITY;
-        const bool warp_cand = !far && (A.flags & DSDF_REPARAM) && warp_weight_positive(G, P, L.ray.o, L.ray.d, tr);
-        need = valid && (warp_cand || (DIRECT ? lit != 0 : (hit && A.integrator == DSDF_SIMPLE_SHADING)));
+        need = !far && needs_backward<DIRECT>(G, P, A, L, tr, lit) && valid;     // (a far sample is a miss that is not lit)
         queue_unit(q, (blockIdx.x * DSDF_BLOCK + threadIdx.x) >> 6, lane, need, lid, tr, DIRECT ? &trs : nullptr,
                    (DIRECT && S.use_mis) ? &trb : nullptr);
     }
@@ -996,8 +998,8 @@ static Workspace carve(void *base, int W, int H, int spp, int nv, int integrator
         }
     }
     if (spp % 64 == 0) {
-        // per group: sub-queue `s` serves the chunks with work-list index % DSDF_TAIL_SUBQ == s; a wave hands off at most
-        // `handoff` rays per 64-sample chunk
+        // per group: a wave hands off at most `handoff` rays per 64-sample chunk; a sub-queue holds its part of an even split of that
+        // worst case (a per-XCD sub-queue has no bound of its own: tail_reserve checks the capacity)
         const size_t handoff = diff ? DSDF_TAIL_HANDOFF : DSDF_PTAIL_HANDOFF;
         ws.tail_words = diff ? DSDF_TAIL_WORDS : DSDF_PTAIL_WORDS;
         ws.tail_cap_sub = (uint32_t)((ws.group_views * Wb * Hb * (size_t)(spp / 64) + DSDF_TAIL_SUBQ - 1) / DSDF_TAIL_SUBQ * handoff);

@@ -1148,4 +1148,33 @@ DSDF_HD void splat_tangent_rgb(float *dblock, int Wb, int Hb, const SampleTangen
     }
 }
 
+// Does a gradient-pass sample go to the backward queue?  It does when its warp term can be non-zero or when its value depends on the
+// SDF: simple shading at a hit; sdf_direct_reparam (DIRECT) when a sampling term is lit (direct_value's result / the shading pass's
+// flag).  EVERY path that can finish a sample asks here -- the fused workers, the general pass, the sweep's tail waves and the
+// wavefront shading pass -- so that they queue the same samples (tests/test_gpu_direct_wavefront.py compares them step for step).
+template <bool DIRECT>
+DSDF_HD bool needs_backward(const GridView &G, const dsdf_params &P, const ViewArgs &A, const Lane &L, const TraceOut &tr, int lit) {
+    const bool hit = tr.its_t < INFINITY;
+    const bool warp_cand = (A.flags & DSDF_REPARAM) && warp_weight_positive(G, P, L.ray.o, L.ray.d, tr);
+    return warp_cand || (DIRECT ? lit != 0 : (hit && A.integrator == DSDF_SIMPLE_SHADING));
+}
+
+// ---------------------------------------------------------------------------
+// The two index maps of the persistent kernels' schedulers.  Plain integer functions, kept here (not beside their device-only users,
+// dsdf_tail.h and the work-list workers of dsdf_kernels.hip) so that the host build can check them: tests/test_sched_maps_host.py.
+// ---------------------------------------------------------------------------
+#define DSDF_TAIL_SUBQ 64           /* tail sub-queues per launch: 8 per XCD (one per ticket counter of the render kernel's XCD share) */
+#ifndef DSDF_ITEM_SEG
+#define DSDF_ITEM_SEG 1024u         /* items per segment = the resident waves of an XCD; the list is tile-major with 1024-chunk tiles
+                                       (measured: 28.9 / 28.7 / 28.6 / 28.5 ms at 256 / 512 / 1024 / 4096) */
+#endif
+// k-th sub-queue a tail block visits when it starts at `first`.  per_xcd (sub-queue = XCD * 8 + ticket counter): the 8 queues of its own
+// XCD (first >> 3) first, then the other XCDs'; else round the ring -- a permutation of all DSDF_TAIL_SUBQ for every `first`
+DSDF_HD uint32_t tail_hop(uint32_t first, uint32_t k, uint32_t per_xcd) {
+    return per_xcd ? (((((first >> 3) + (k >> 3)) & 7u) << 3) | ((first + k) & 7u)) : ((first + k) & (DSDF_TAIL_SUBQ - 1u));
+}
+// j-th work item of share `sh` (0..7): the work list is cut into segments of DSDF_ITEM_SEG items and segment s belongs to share s % 8.
+// Ascending in j, so a share is exhausted at its first item >= the number of items.
+DSDF_HD uint32_t item_of(uint32_t sh, uint32_t j) { return ((j / DSDF_ITEM_SEG) * 8u + sh) * DSDF_ITEM_SEG + j % DSDF_ITEM_SEG; }
+
 }  // namespace dsdf

@@ -14,9 +14,9 @@
 //
 // A tail kernel is bound by the LATENCY of its longest rays (2000+ dependent steps of ~1.8 us on an otherwise empty chip), so it
 // runs ONE wave per SIMD (DSDF_TAIL_BLOCKS_PER_SUBQ): every further resident wave slows that chain down.  Round 3's counters
-// (profiles/r03_sq.json) showed what the memory system saw: sub-queue = work-list index % 64 meant that a tail wave drained
-// rays of all 8 tiles in flight (one per XCD) and of all views -- 51 % L2 misses, 9.95 GB fetched per launch.  The sub-queues are
-// per XCD now: a render wave appends to queue (its XCC_ID, its ticket counter), i.e. in the order in which its XCD walks the
+// (profiles/r03_sq.json) showed what the memory system saw: sub-queue = work-list index % 64 (the layout of that round,
+// per_xcd = 0) meant that a tail wave drained rays of all 8 tiles in flight (one per XCD) and of all views -- 51 % L2 misses, 9.95 GB
+// fetched per launch.  The sub-queues are per XCD: a render wave appends to queue (its XCC_ID, its ticket counter), i.e. in the order in which its XCD walks the
 // tiles, and a tail block drains the queues of the XCD it runs on first (then helps the others: every queue is drained
 // whatever the block -> XCD mapping is): 18 % misses, 0.8 GB, and -- with one wave per SIMD -- 0.4 ms off the step
 // (profiles/r04_tail_ab.md; with 4096 tail waves the same mapping was slower: a hard tile's rays land on an eighth of the waves).
@@ -51,7 +51,6 @@
 #ifndef DSDF_TAIL_CNT_STRIDE
 #define DSDF_TAIL_CNT_STRIDE 32     /* uint32 words between the {queued, claimed} pairs of two sub-queues: a 128-byte line each (2 = packed, as before round 5) */
 #endif
-#define DSDF_TAIL_SUBQ 64           /* sub-queues per launch: 8 per XCD (one per ticket counter of the render kernel's XCD share) */
 #ifndef DSDF_TAIL_REFILL
 #define DSDF_TAIL_REFILL 24         /* idle lanes that trigger a refill in the tail kernels */
 #endif
@@ -71,16 +70,15 @@ __device__ __forceinline__ uint32_t xcc_id() {
 }
 // sub-queue of a render worker / first sub-queue of a tail block: (XCD, blockIdx.x / 8 mod 8)
 __device__ __forceinline__ uint32_t tail_subq() { return (xcc_id() << 3) | ((blockIdx.x >> 3) & 7u); }
-// k-th sub-queue a tail block visits.  per XCD: the 8 queues of its own XCD first, then the other XCDs'; else round the ring
-__device__ __forceinline__ uint32_t tail_hop(uint32_t first, uint32_t k, uint32_t per_xcd) {
-    return per_xcd ? (((((first >> 3) + (k >> 3)) & 7u) << 3) | ((first + k) & 7u)) : ((first + k) & (DSDF_TAIL_SUBQ - 1u));
-}
+// (the order in which a tail block visits the sub-queues: tail_hop, dsdf_lane.h)
 
+// DSDF_TAIL_SUBQ sub-queues; a producer appends to sub-queue (the XCD it runs on, its ticket counter): tail_subq()
 struct TailQueue {
     uint32_t *count;   // [DSDF_TAIL_SUBQ][DSDF_TAIL_CNT_STRIDE]: {queued, claimed, padding}
     float *state;      // [DSDF_TAIL_SUBQ][cap_sub][words] march states
     uint32_t cap_sub;
-    uint32_t per_xcd;  // 1: sub-queue = (XCD of the producer, ticket counter); 0: sub-queue = work-list index % DSDF_TAIL_SUBQ
+    uint32_t per_xcd;  // constant 1 (sub-queue = (XCD of the producer, ticket counter)); 0 was the round-3 layout, work-list index % DSDF_TAIL_SUBQ.
+                       // Removing the field is not timed yet: it moves the allocation of the 64-VGPR kernels (profiles/r07_shared_device_ab.md)
 };
 
 // One reservation per wave in sub-queue `sub`: `n` consecutive entries, or nothing when they do not fit (compare-and-swap, so a
@@ -174,29 +172,69 @@ struct HandOffCtl {
 typedef HandOffCtl<DSDF_TAIL_HANDOFF, DSDF_TAIL_GRACE> HandOff;
 typedef HandOffCtl<DSDF_PTAIL_HANDOFF, DSDF_PTAIL_GRACE> PlainHandOff;
 
-// refill of a persistent tail wave: the idle lanes claim the next queued entries; returns this lane's entry or ~0u
-__device__ __forceinline__ uint32_t tail_claim(uint32_t *cnt, uint32_t total, uint64_t idle, bool mine, bool &exhausted) {
-    uint32_t base = 0;
-    const int leader = __builtin_ctzll(idle);
-    if (lane_id() == leader) base = atomicAdd(cnt + 1, (uint32_t)__popcll(idle));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    if (base >= total) exhausted = true;
-    const uint32_t idx = base + mask_prefix(idle);
-    if (base + (uint32_t)__popcll(idle) >= total) exhausted = true;      // (everything queued has been claimed)
-    return (mine && idx < total) ? idx : ~0u;
-}
+// Where a persistent consumer (the two tail kernels, the two shadow streams) stands in the DSDF_TAIL_SUBQ sub-queues: it visits them in
+// the order tail_hop(first, 0), tail_hop(first, 1), ... and skips those with nothing left to claim, so every sub-queue is drained
+// whatever the block -> XCD mapping is.  WORDS: floats per entry (DSDF_TAIL_WORDS / DSDF_PTAIL_WORDS).
+// The {queued, claimed} counters move under device-scope atomics of other waves: open_next reads them with ATOMIC loads, not cached ones.
+template <uint32_t WORDS>
+struct SubqCursor {
+    uint32_t first;             // sub-queue visited first
+    uint32_t hop = 0;           // sub-queues visited so far (DSDF_TAIL_SUBQ: none is left)
+    uint32_t total = 0;         // entries queued in the open sub-queue
+    uint32_t *cnt = nullptr;    // its {queued, claimed} pair
+    const float *ent = nullptr; // its entries
+    // opens the next sub-queue with unclaimed entries; false when there is none left
+    __device__ __forceinline__ bool open_next(const TailQueue &tq) {
+        // lane k looks at the sub-queue this wave would visit k-th: one round trip for all of them
+        const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
+        uint32_t *c = tq.count + DSDF_TAIL_CNT_STRIDE * sub_k;
+        const uint32_t queued = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t claimed = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint64_t open = __ballot(claimed < queued);
+        open = hop < 64u ? (open >> hop) << hop : 0ull;
+        if (open == 0) { hop = DSDF_TAIL_SUBQ; return false; }
+        const int k = __builtin_ctzll(open);
+        hop = (uint32_t)k + 1u;
+        const uint32_t sub = tail_hop(first, (uint32_t)k, tq.per_xcd);
+        cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
+        ent = tq.state + (size_t)sub * tq.cap_sub * WORDS;
+        total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
+        return true;
+    }
+    // refill: the idle lanes claim the next queued entries of the open sub-queue; returns this lane's entry index or ~0u, `e` = the
+    // entry.  The entry pointer is taken BEFORE the queue is switched; a drained queue is left here, so that the next refill takes
+    // the next one (`exhausted`: there is none).
+    __device__ __forceinline__ uint32_t claim(const TailQueue &tq, uint64_t idle, bool mine, bool &exhausted, const float *&e) {
+        uint32_t base = 0;
+        const int leader = __builtin_ctzll(idle);
+        if (lane_id() == leader) base = atomicAdd(cnt + 1, (uint32_t)__popcll(idle));
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+        const uint32_t mine_idx = base + mask_prefix(idle);
+        const uint32_t idx = (mine && mine_idx < total) ? mine_idx : ~0u;
+        e = ent + (size_t)idx * WORDS;
+        if (base + (uint32_t)__popcll(idle) >= total) exhausted = !open_next(tq);     // (everything queued has been claimed)
+        return idx;
+    }
+};
 
-// tail statistics (slots 8..10 of the caller's stats rows, include/dsdf.h): lane-steps, lock-step iterations, rays
-// Slots 11..15 of rows 0..3: diagnostics of the tail waves of ONE launch (include/dsdf.h: dsdf_tail_stats_arm lists them).
-__device__ __forceinline__ void tail_stats(unsigned long long *stats, int lane_steps, int wave_steps, int rays, unsigned long long t0,
-                                           unsigned long long c0, unsigned long long c_refill, const unsigned long long *sec, int row) {
+// slots 8..10 of the caller's stats rows (include/dsdf.h) -- lane-steps, lock-step iterations, rays of a persistent consumer
+__device__ __forceinline__ void stream_stats(unsigned long long *stats, int lane_steps, int wave_steps, int rays) {
     const int ls = wave_sum_i32(lane_steps), r = wave_sum_i32(rays);
-    const unsigned long long dt = wall_clock64() - t0, dc = (unsigned long long)clock64() - c0;
     if (lane_id() == 0) {
         unsigned long long *st = stats + (size_t)(blockIdx.x & 63u) * DSDF_STAT_SLOTS;
         atomicAdd(st + 8, (unsigned long long)ls);
         atomicAdd(st + 9, (unsigned long long)wave_steps);
         atomicAdd(st + 10, (unsigned long long)r);
+    }
+}
+
+// tail statistics: stream_stats, and
+// slots 11..15 of rows 0..3: diagnostics of the tail waves of ONE launch (include/dsdf.h: dsdf_tail_stats_arm lists them).
+__device__ __forceinline__ void tail_stats(unsigned long long *stats, int lane_steps, int wave_steps, int rays, unsigned long long t0,
+                                           unsigned long long c0, unsigned long long c_refill, const unsigned long long *sec, int row) {
+    const unsigned long long dt = wall_clock64() - t0, dc = (unsigned long long)clock64() - c0;
+    stream_stats(stats, lane_steps, wave_steps, rays);
+    if (lane_id() == 0) {
         atomicMax(stats + 11, (unsigned long long)wave_steps);
         atomicMax(stats + 12, dt);
         atomicAdd(stats + 13, dt);
@@ -230,33 +268,12 @@ template <bool STORE>
 __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params P, ViewBatch VB, float *__restrict__ blocks,
                                                          TailQueue tq, Queue qall, unsigned long long *stats) {
     __builtin_amdgcn_s_setprio(DSDF_TAIL_PRIO);
-    const uint32_t first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
-    uint32_t hop = 0, total = 0;
-    uint32_t *cnt = nullptr;
-    const float *ent = nullptr;
-    // opens the next sub-queue with unclaimed entries; false when there is none left
-    auto open_next = [&]() {
-        // lane k looks at the sub-queue this wave would visit k-th: one round trip for all of them (the claimed counters move under
-        // device-scope atomics of other waves: an atomic load, not a cached one)
-        const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
-        uint32_t *c = tq.count + DSDF_TAIL_CNT_STRIDE * sub_k;
-        const uint32_t queued = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t claimed = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t open = __ballot(claimed < queued);
-        open = hop < 64u ? (open >> hop) << hop : 0ull;
-        if (open == 0) { hop = DSDF_TAIL_SUBQ; return false; }
-        const int k = __builtin_ctzll(open);
-        hop = (uint32_t)k + 1u;
-        const uint32_t sub = tail_hop(first, (uint32_t)k, tq.per_xcd);
-        cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-        ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_TAIL_WORDS;
-        total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
-        return true;
-    };
+    SubqCursor<DSDF_TAIL_WORDS> cur;
+    cur.first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
     DSDF_TAIL_VIEWS_LDS(VB, views);
     const unsigned long long t_start = stats ? wall_clock64() : 0ull, c_start = stats ? (unsigned long long)clock64() : 0ull;
     unsigned long long c_refill = 0, c_sec[5] = {0, 0, 0, 0, 0};
-    if (!open_next()) return;
+    if (!cur.open_next(tq)) return;
     DiffMarch m;
     m.active = false;
     Lane L;
@@ -286,8 +303,7 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
         }
         const bool hit = tr.its_t < INFINITY;
         n_hits += hit ? 1 : 0;
-        const bool warp_cand = (A.flags & DSDF_REPARAM) && warp_weight_positive(G, P, L.ray.o, L.ray.d, tr);
-        if (warp_cand || (hit && A.integrator == DSDF_SIMPLE_SHADING)) {
+        if (needs_backward<false>(G, P, A, L, tr, 0)) {
             const Queue qv = view_queue(qall, view);
             const uint32_t unit = sample >> 6;
             const uint32_t slot = atomicAdd(qv.count + unit, 1u);   // behind the entries the sweep compacted
@@ -306,10 +322,8 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
             const unsigned long long c_in = stats ? (unsigned long long)clock64() : 0ull;
             if (done) { complete(); done = false; }
             const unsigned long long c_a = stats ? (unsigned long long)clock64() : 0ull;
-            bool drained = false;
-            const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
-            const float *e = ent + (size_t)idx * DSDF_TAIL_WORDS;       // (read below, before the queue is switched)
-            if (drained) exhausted = !open_next();                       // this queue is done: the next refill takes the next one
+            const float *e;
+            const uint32_t idx = cur.claim(tq, idle, !m.active, exhausted, e);
             const unsigned long long c_b = stats ? (unsigned long long)clock64() : 0ull;
             if (idx != ~0u) {
                 view = __float_as_uint(e[0]);
@@ -365,32 +379,12 @@ __global__ __launch_bounds__(256) void k_tail_trace_diff(GridView G, dsdf_params
 __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_params P, ViewBatch VB, float *__restrict__ blocks,
                                                           TailQueue tq, unsigned long long *stats, float *__restrict__ hit_t) {
     __builtin_amdgcn_s_setprio(DSDF_TAIL_PRIO);
-    const uint32_t first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
-    uint32_t hop = 0, total = 0;
-    uint32_t *cnt = nullptr;
-    const float *ent = nullptr;
-    auto open_next = [&]() {
-        // lane k looks at the sub-queue this wave would visit k-th: one round trip for all of them (the claimed counters move under
-        // device-scope atomics of other waves: an atomic load, not a cached one)
-        const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
-        uint32_t *c = tq.count + DSDF_TAIL_CNT_STRIDE * sub_k;
-        const uint32_t queued = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t claimed = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t open = __ballot(claimed < queued);
-        open = hop < 64u ? (open >> hop) << hop : 0ull;
-        if (open == 0) { hop = DSDF_TAIL_SUBQ; return false; }
-        const int k = __builtin_ctzll(open);
-        hop = (uint32_t)k + 1u;
-        const uint32_t sub = tail_hop(first, (uint32_t)k, tq.per_xcd);
-        cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-        ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_PTAIL_WORDS;
-        total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
-        return true;
-    };
+    SubqCursor<DSDF_PTAIL_WORDS> cur;
+    cur.first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
     DSDF_TAIL_VIEWS_LDS(VB, views);
     const unsigned long long t_start = stats ? wall_clock64() : 0ull, c_start = stats ? (unsigned long long)clock64() : 0ull;
     unsigned long long c_refill = 0, c_sec[5] = {0, 0, 0, 0, 0};
-    if (!open_next()) return;
+    if (!cur.open_next(tq)) return;
     PlainMarch m;
     m.active = false;
     Lane L;
@@ -406,7 +400,7 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
         int nref;
         const float its_t = refine_hit(G, P, m.o, m.d, m.its_t, m.trace_eps, nref, D);
         if (hit_t) {
-            hit_t[(size_t)view * ((size_t)(A.Wb * A.Hb) * (uint32_t)A.spp) + sample] = its_t;
+            hit_t[hit_slot((size_t)(A.Wb * A.Hb), A.spp, view, sample)] = its_t;
             ++n_hits; n_ref += nref;
             return;
         }
@@ -425,10 +419,8 @@ __global__ __launch_bounds__(256) void k_tail_trace_plain(GridView G, dsdf_param
             const unsigned long long c_in = stats ? (unsigned long long)clock64() : 0ull;
             if (done) { complete(); done = false; }
             const unsigned long long c_a = stats ? (unsigned long long)clock64() : 0ull;
-            bool drained = false;
-            const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
-            const float *e = ent + (size_t)idx * DSDF_PTAIL_WORDS;      // (read below, before the queue is switched)
-            if (drained) exhausted = !open_next();
+            const float *e;
+            const uint32_t idx = cur.claim(tq, idle, !m.active, exhausted, e);
             const unsigned long long c_b = stats ? (unsigned long long)clock64() : 0ull;
             if (idx != ~0u) {
                 view = __float_as_uint(e[0]);
@@ -559,28 +551,10 @@ __global__ void k_cell_table(const float *__restrict__ padded, int sx, int sy, i
 template <bool TABLE>
 __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P, ViewBatch VB, TailQueue tq, float *__restrict__ hit_t,
                                                        unsigned long long *stats, const float *__restrict__ cell_table) {
-    const uint32_t first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
-    uint32_t hop = 0, total = 0;
-    uint32_t *cnt = nullptr;
-    const float *ent = nullptr;
-    auto open_next = [&]() {
-        const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
-        uint32_t *c = tq.count + DSDF_TAIL_CNT_STRIDE * sub_k;
-        const uint32_t queued = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t claimed = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t open = __ballot(claimed < queued);
-        open = hop < 64u ? (open >> hop) << hop : 0ull;
-        if (open == 0) { hop = DSDF_TAIL_SUBQ; return false; }
-        const int k = __builtin_ctzll(open);
-        hop = (uint32_t)k + 1u;
-        const uint32_t sub = tail_hop(first, (uint32_t)k, tq.per_xcd);
-        cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-        ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_PTAIL_WORDS;
-        total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
-        return true;
-    };
+    SubqCursor<DSDF_PTAIL_WORDS> cur;
+    cur.first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
     DSDF_TAIL_VIEWS_LDS(VB, views);
-    if (!open_next()) return;
+    if (!cur.open_next(tq)) return;
     dsdf_params Ps = P;
     Ps.refine_steps = 0;
     PlainMarch m;
@@ -594,10 +568,8 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
     while (true) {
         const uint64_t idle = __ballot(!m.active);
         if (!exhausted && __popcll(idle) >= DSDF_SHQ_REFILL) {
-            bool drained = false;
-            const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
-            const float *e = ent + (size_t)idx * DSDF_PTAIL_WORDS;      // (read below, before the queue is switched)
-            if (drained) exhausted = !open_next();
+            const float *e;
+            const uint32_t idx = cur.claim(tq, idle, !m.active, exhausted, e);
             if (idx != ~0u) {
                 const uint32_t view = __float_as_uint(e[0]), sample = __float_as_uint(e[1]);
                 my_t = e[2];
@@ -606,7 +578,7 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
                 DirectHit h;
                 direct_setup(G, A, L, sample, my_t, h);
                 m = plain_march_begin(Ps, h.sr.o, h.sr.d, h.sr.maxt);
-                slot = (size_t)view * ((size_t)(A.Wb * A.Hb) * (uint32_t)A.spp) + sample;
+                slot = hit_slot((size_t)(A.Wb * A.Hb), A.spp, view, sample);
                 F.valid = false;
                 ++n_rays;
             }
@@ -625,15 +597,7 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
             if (!m.active && m.its_t < INFINITY) hit_t[slot] = -my_t;       // occluded
         }
     }
-    if (stats) {
-        const int ls = wave_sum_i32(n_steps), r = wave_sum_i32(n_rays);
-        if (lane_id() == 0) {
-            unsigned long long *st = stats + (size_t)(blockIdx.x & 63u) * DSDF_STAT_SLOTS;
-            atomicAdd(st + 8, (unsigned long long)ls);
-            atomicAdd(st + 9, (unsigned long long)n_wsteps);
-            atomicAdd(st + 10, (unsigned long long)r);
-        }
-    }
+    if (stats) stream_stats(stats, n_steps, n_wsteps, n_rays);
 }
 
 // The same stream for the gradient sweep: the differentiable march of the listed shadow rays (ray_intersect with the warp
@@ -642,28 +606,10 @@ __global__ __launch_bounds__(256) void k_shadow_stream(GridView G, dsdf_params P
 // goes to rows 9..17 of the sample's backward-queue record, where the shading pass and k_backward<true> read it.
 __global__ __launch_bounds__(256) void k_shadow_stream_diff(GridView G, dsdf_params P, ViewBatch VB, TailQueue tq, Queue qall,
                                                             unsigned long long *stats) {
-    const uint32_t first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
-    uint32_t hop = 0, total = 0;
-    uint32_t *cnt = nullptr;
-    const float *ent = nullptr;
-    auto open_next = [&]() {
-        const uint32_t sub_k = tail_hop(first, (uint32_t)lane_id(), tq.per_xcd);
-        uint32_t *c = tq.count + DSDF_TAIL_CNT_STRIDE * sub_k;
-        const uint32_t queued = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t claimed = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t open = __ballot(claimed < queued);
-        open = hop < 64u ? (open >> hop) << hop : 0ull;
-        if (open == 0) { hop = DSDF_TAIL_SUBQ; return false; }
-        const int k = __builtin_ctzll(open);
-        hop = (uint32_t)k + 1u;
-        const uint32_t sub = tail_hop(first, (uint32_t)k, tq.per_xcd);
-        cnt = tq.count + DSDF_TAIL_CNT_STRIDE * sub;
-        ent = tq.state + (size_t)sub * tq.cap_sub * DSDF_PTAIL_WORDS;
-        total = (uint32_t)__builtin_amdgcn_readlane((int)queued, k);
-        return true;
-    };
+    SubqCursor<DSDF_PTAIL_WORDS> cur;
+    cur.first = tq.per_xcd ? tail_subq() : blockIdx.x % DSDF_TAIL_SUBQ;
     DSDF_TAIL_VIEWS_LDS(VB, views);
-    if (!open_next()) return;
+    if (!cur.open_next(tq)) return;
     dsdf_params Ps = P;
     Ps.refine_steps = 0;
     const bool keep_warp = reparam_depth1(P);
@@ -686,10 +632,8 @@ __global__ __launch_bounds__(256) void k_shadow_stream_diff(GridView G, dsdf_par
         const uint64_t idle = __ballot(!m.active);
         if (!exhausted && __popcll(idle) >= DSDF_SHQ_REFILL) {
             if (pending) { complete(); pending = false; }
-            bool drained = false;
-            const uint32_t idx = tail_claim(cnt, total, idle, !m.active, drained);
-            const float *e = ent + (size_t)idx * DSDF_PTAIL_WORDS;
-            if (drained) exhausted = !open_next();
+            const float *e;
+            const uint32_t idx = cur.claim(tq, idle, !m.active, exhausted, e);
             if (idx != ~0u) {
                 const uint32_t view = __float_as_uint(e[0]), sample = __float_as_uint(e[1]);
                 const float its_t = e[2];
@@ -721,13 +665,5 @@ __global__ __launch_bounds__(256) void k_shadow_stream_diff(GridView G, dsdf_par
         }
     }
     if (pending) complete();
-    if (stats) {
-        const int ls = wave_sum_i32(n_steps), r = wave_sum_i32(n_rays);
-        if (lane_id() == 0) {
-            unsigned long long *st = stats + (size_t)(blockIdx.x & 63u) * DSDF_STAT_SLOTS;
-            atomicAdd(st + 8, (unsigned long long)ls);
-            atomicAdd(st + 9, (unsigned long long)n_wsteps);
-            atomicAdd(st + 10, (unsigned long long)r);
-        }
-    }
+    if (stats) stream_stats(stats, n_steps, n_wsteps, n_rays);
 }

@@ -587,4 +587,9 @@ void hh_trace_hits(const float *data, int rx, int ry, int rz, const dsdf_params 
     }
 }
 
+// The two index maps of the persistent kernels' schedulers (csrc/dsdf_lane.h: tail_hop, item_of) and the segment length of the work list.
+int hh_tail_hop(int first, int k) { return (int)tail_hop((uint32_t)first, (uint32_t)k, 1u); }
+int hh_item_of(int share, int j) { return (int)item_of((uint32_t)share, (uint32_t)j); }
+int hh_item_seg() { return (int)DSDF_ITEM_SEG; }
+
 }  // extern "C"

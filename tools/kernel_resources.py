@@ -30,8 +30,10 @@ for line in r.stdout.splitlines():
     elif cur is not None and ':' in t:
         k, v = t.split(':', 1)
         cur[k.strip()] = v.strip()
-print(f"{'kernel':58s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'scratch':>8s} {'occ':>4s} {'LDS':>7s}")
+print(f"{'kernel':58s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'scratch':>8s} {'occ':>4s} {'LDS':>7s} {'Sspill':>6s} {'Vspill':>6s}")
 for c in rows:
     if flt in c['name']:
-        print(f"{c['name'][:58]:58s} {c.get('VGPRs', '?'):>5s} {c.get('AGPRs', '?'):>5s} {c.get('SGPRs', '?'):>5s} "
-              f"{c.get('ScratchSize [bytes/lane]', '?'):>8s} {c.get('Occupancy [waves/SIMD]', '?'):>4s} {c.get('LDS Size [bytes/block]', '?'):>7s}")
+        # (the compiler's remark is `TotalSGPRs`; older ones said `SGPRs`)
+        print(f"{c['name'][:58]:58s} {c.get('VGPRs', '?'):>5s} {c.get('AGPRs', '?'):>5s} {c.get('TotalSGPRs', c.get('SGPRs', '?')):>5s} "
+              f"{c.get('ScratchSize [bytes/lane]', '?'):>8s} {c.get('Occupancy [waves/SIMD]', '?'):>4s} {c.get('LDS Size [bytes/block]', '?'):>7s} "
+              f"{c.get('SGPRs Spill', '?'):>6s} {c.get('VGPRs Spill', '?'):>6s}")
