@@ -4,6 +4,7 @@
 //   dsdf_film.h                wave-level film splat, develop kernels (+ adjoint / tangent)
 //   dsdf_skip.h                exact empty-space proof (coarse min-grids, per-pixel flags)
 //   dsdf_redistance.h          Eikonal redistancing kernels + entry points
+//   dsdf_eikonal.h             host/device arithmetic of one redistancing voxel (also compiled by the host-side tests)
 //   this file                  render pass, backward / forward-tangent sweeps, workspace, C-ABI
 //
 // Kernel inventory (DESIGN.md section 4 has the roofline for each):
