@@ -3,11 +3,17 @@
 #pragma once
 
 // Film splat of one wave whose 64 samples belong to ONE pixel (px,py): their contributions fall into the 5x5 block-pixel
-// window around it.  film_accum_wave reduces the 25 (x NCH channels) partial sums across the wave through a wave-private
-// LDS transpose (lane l writes column l, lane k sums row k with 16 conflict-free ds_read_b128; two chunks of <= 13 rows)
-// and ADDS them to acc[ch][chunk] of lanes 0..12 -- so that a wave which renders several 64-sample chunks of the same
-// pixel (spp 256 = 4 chunks) touches memory once per pixel: film_flush_wave then issues one atomic per window pixel and
-// channel (PMC, round 1: the primal launch wrote 8.1 GB for a 25 MB film with one flush per chunk).
+// window around it, and the wave reduces them before it touches memory -- one atomic per window pixel and channel instead
+// of one per sample (PMC, round 1: the primal launch wrote 8.1 GB for a 25 MB film).  A work item of the persistent
+// kernels is ONE 64-sample chunk of a pixel and flushes its window when it is done; only the shading pass of the wavefront
+// sdf_direct_reparam, which has no march (k_direct_items<1>), takes a pixel as one item whose spp / 64 chunks add up in
+// registers before the one flush.  Two reductions:
+//   film_reduce_mfma      the primal of the one-channel integrators (value, weight): the window sums of a chunk are a
+//                         10 x 64 by 64 x 5 product, done by the matrix pipe while the vector pipe goes on (below)
+//   film_accum_wave<NCH>  the gradient sweep (NCH = 2) and sdf_direct_reparam (NCH = 4): a wave-private LDS transpose (lane l
+//                         writes column l, lane k sums row k with 16 conflict-free ds_read_b128; two chunks of <= 13 rows),
+//                         sums in acc[ch][chunk] of lanes 0..12, flushed by film_flush_wave.  (The sweep runs at 3 waves per
+//                         SIMD with 167 registers: the MFMA form was measured there and showed no gain)
 template <int NCH>     // block channels: NCH - 1 value channels + weight
 __device__ __forceinline__ void film_accum_wave(int px, int py, float u, float v, const float *vals, float *T, int lid,
                                                 float acc[NCH][2]) {
@@ -80,66 +86,79 @@ __device__ __forceinline__ void film_accum_wave(int px, int py, float u, float v
     }
 }
 
-// The 5 x 5 film window of the 64 samples of one chunk from their film offsets (r0, r1) in [0, 1)^2.  A PRIMAL sample is splatted
-// where it was generated: without a reparameterisation `sensor.sample_direction(o + d)` (reparam.py:99-118) returns the film position
-// the ray was sampled at -- exactly, in real arithmetic: (near_t + 1) d_local projects to the pixel position d_local was built from --
-// so the window weights follow from the sampler's offsets alone and neither a camera ray nor a re-projection is computed for the
-// samples of a chunk whose march is proven away (dsdf_proof.h).  (Against the re-projected position of round 4 the weights move by
-// the fp32 rounding of that projection, ~1e-7: image sums agree to 7e-8.)  The the sample sits at block
-// position (px + r0 - 0.5, py + r1 - 0.5), window pixel (px - 2 + i, py - 2 + j) is (i - 1.5 - r0, j - 1.5 - r1) away.  `on`:
-// lanes that are off contribute nothing.  Same wave-level reduction as film_accum_wave (dsdf_film.h).
-__device__ __forceinline__ void film_accum_offsets(float r0, float r1, bool on, float val, float *T, int lid, float acc[2][2]) {
+// Two-channel window sums of one 64-sample chunk on the matrix pipe.  With the weights separable, f = fx[i] fy[j], the sums are
+//   S[2 j + c][i] = sum over the samples l of A[2 j + c][l] * B[l][i],    A[2 j][l] = fy[j] val (value), A[2 j + 1][l] = fy[j]
+//   (weight), B[l][i] = fx[i],
+// a 10 x 64 by 64 x 5 product inside the 16 x 16 tile of v_mfma_f32_16x16x4_f32.  The vector pipe, which bounds this
+// kernel, pays the ten Gaussians, 15 LDS writes, 8 ds_read_b128 and a handful of adds; the 16 MFMAs run beside it.
+//   1. lane l writes its 15 numbers as column l of 15 LDS rows (10 A rows, 5 B rows, stride DSDF_TSTRIDE);
+//   2. lane (m = l & 15, kk = l >> 4) reads samples 16 kk .. 16 kk + 15 of A row m and of B row m (rows beyond the 10 / 5 used ones
+//      are clamped: they feed tile entries nobody reads); MFMA t takes sample 16 kk + t as its k = kk -- which sample sits at which
+//      k is free as long as A and B agree;
+//   3. 16 MFMAs in two independent chains that start from zero (dependent latency 40 cycles, issue interval 32), added at the end;
+//      an f32 MFMA is a k-ordered fmaf chain, so a chunk's sums are the same bits wherever and whenever the chunk is reduced;
+//   4. register r of lane l then holds S[4 (l >> 4) + r][l & 15]: lane (kk, i) owns window pixels (i, 2 kk) and (i, 2 kk + 1), value
+//      and weight side by side, and adds them to its win[4].  x runs along the lanes so that a flush touches 5 film rows.
+// A chunk whose values are all 1 has value rows equal to its weight rows operand for operand: both channels come out as the same
+// bits (the DSDF_PX_ONE argument of dsdf_skip.h); one whose values are all 0 has value sums +0, which the flush leaves out.
+// Must be reached in wave-uniform control flow with all 64 lanes active.
+typedef float film_f32x4 __attribute__((ext_vector_type(4)));
+#define DSDF_FILM_ROWS 15     /* 10 A rows + 5 B rows of the MFMA film reduction; 15 * DSDF_TSTRIDE <= DSDF_WAVE_LDS */
+__device__ __forceinline__ void film_reduce_mfma(const float fx[5], const float fy[5], float val, float *T, int lid, float win[4]) {
+    static_assert(DSDF_FILM_ROWS * DSDF_TSTRIDE <= DSDF_WAVE_LDS, "the film rows live in the wave's LDS scratch");
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        T[(2 * j) * DSDF_TSTRIDE + lid] = fy[j] * val;
+        T[(2 * j + 1) * DSDF_TSTRIDE + lid] = fy[j];
+        T[(10 + j) * DSDF_TSTRIDE + lid] = fx[j];
+    }
+    wave_lds_sync();
+    const int m = lid & 15, kk = lid >> 4;
+    const float4 *ra = reinterpret_cast<const float4 *>(T + (m < 10 ? m : 9) * DSDF_TSTRIDE + 16 * kk);
+    const float4 *rb = reinterpret_cast<const float4 *>(T + (10 + (m < 5 ? m : 4)) * DSDF_TSTRIDE + 16 * kk);
+    film_f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {        // one A quad and one B quad at a time: 8 operand registers live
+        const float4 a = ra[q], b = rb[q];
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c1, 0, 0, 0);
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) win[r] += c0[r] + c1[r];
+    wave_lds_sync();                     // (the rows are rewritten by the next chunk / the next item's cell cache)
+}
+
+// The window of a PRIMAL chunk from the film offsets (r0, r1) in [0, 1)^2 of its samples.  A primal sample is splatted where it was
+// generated: without a reparameterisation `sensor.sample_direction(o + d)` (reparam.py:99-118) returns the film position the ray was
+// sampled at -- exactly, in real arithmetic: (near_t + 1) d_local projects to the pixel position d_local was built from -- so the
+// window weights follow from the sampler's offsets alone and neither a camera ray nor a re-projection is computed for the samples of
+// a chunk whose march is proven away (dsdf_proof.h).  (Against the re-projected position of round 4 the weights move by the fp32
+// rounding of that projection, ~1e-7: image sums agree to 7e-8.)  The sample sits at block position (px + r0 - 0.5, py + r1 - 0.5),
+// window pixel (px - 2 + i, py - 2 + j) is (i - 1.5 - r0, j - 1.5 - r1) away.
+__device__ __forceinline__ void film_accum_offsets(float r0, float r1, float val, float *T, int lid, float win[4]) {
     float fx[5], fy[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        fx[i] = on ? gauss_f(((float)i - 1.5f) - r0) : 0.f;
+        fx[i] = gauss_f(((float)i - 1.5f) - r0);
         fy[i] = gauss_f(((float)i - 1.5f) - r1);
     }
-    float f[25];
+    film_reduce_mfma(fx, fy, val, T, lid, win);
+}
+
+// Flush of win[4] (film_reduce_mfma, item 4): the 15 lanes (kk < 3, i < 5) that hold window entries issue at most 10 rows x 5 columns =
+// 50 atomics, inside the film block and non-zero only.
+__device__ __forceinline__ void film_flush_mfma(float *__restrict__ block, const ViewArgs &A, int px, int py, int lid, const float win[4]) {
+    const int i = lid & 15, qx = px - 2 + i;
+    const bool col = i < 5 && qx >= 0 && qx < A.Wb;
 #pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) f[j * 5 + i] = fx[i] * fy[j];
-    // (lanes that are off carry f == 0: any value gives 0; 1 keeps the all-one shortcut of hit-only events)
-    const float vv = on ? val : 1.f;
-    const bool all_one = __ballot(vv != 1.f) == 0;
-    const bool any_val = __ballot(on && vv != 0.f) != 0;
-    float wsum[2] = {0.f, 0.f};
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-        const int ch = cc == 0 ? 1 : 0;                      // weight channel first
-        const float s = ch == 0 ? vv : 1.f;
-        if (ch == 0 && all_one) {
-            if (lid < DSDF_TROWS) { acc[0][0] += wsum[0]; acc[0][1] += wsum[1]; }
-            continue;
-        }
-        if (ch == 0 && !any_val) continue;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int k0 = c * DSDF_TROWS;
-            const int nk = (25 - k0) < DSDF_TROWS ? (25 - k0) : DSDF_TROWS;
-#pragma unroll
-            for (int k = 0; k < DSDF_TROWS; ++k)
-                if (k < nk) T[k * DSDF_TSTRIDE + lid] = f[k0 + k] * s;
-            wave_lds_sync();
-            if (lid < nk) {
-                const float4 *row = reinterpret_cast<const float4 *>(T + lid * DSDF_TSTRIDE);
-                float4 a0 = row[0], a1 = row[1], a2 = row[2], a3 = row[3];
-#pragma unroll
-                for (int r = 4; r < 16; r += 4) {
-                    float4 b0 = row[r], b1 = row[r + 1], b2 = row[r + 2], b3 = row[r + 3];
-                    a0.x += b0.x; a0.y += b0.y; a0.z += b0.z; a0.w += b0.w;
-                    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                    a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-                    a3.x += b3.x; a3.y += b3.y; a3.z += b3.z; a3.w += b3.w;
-                }
-                const float sum = ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w)) +
-                                  (((a2.x + a2.y) + (a2.z + a2.w)) + ((a3.x + a3.y) + (a3.z + a3.w)));
-                acc[ch][c] += sum;
-                if (ch == 1) wsum[c] = sum;
-            }
-            wave_lds_sync();
-        }
+    for (int p = 0; p < 2; ++p) {
+        const int j = 2 * (lid >> 4) + p, qy = py - 2 + j;
+        const bool own = col && j < 5 && qy >= 0 && qy < A.Hb;
+        float *dst = block + 2 * ((size_t)(own ? qy : 0) * A.Wb + (own ? qx : 0));
+        if (own && win[2 * p] != 0.f) atomicAdd(dst, win[2 * p]);
+        if (own && win[2 * p + 1] != 0.f) atomicAdd(dst + 1, win[2 * p + 1]);
     }
 }
 

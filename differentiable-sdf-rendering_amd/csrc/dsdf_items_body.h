@@ -1,7 +1,8 @@
 // dsdf_items_body.h -- the body of the persistent work-list workers, included TWICE by dsdf_kernels.hip: as k_render_items<DIFF, DIRECT,
 // STATS> (STORE_T = false) and as k_render_items_store<DIFF, STATS> (DIRECT = false, STORE_T = true: the march of the primary rays of
 // the wavefront sdf_direct_reparam).  Textual inclusion rather than a shared device function: the 64-register primal
-// kernel's allocation is sensitive to how its parameters arrive (a by-reference / by-value wrapper moved 68 bytes of scratch to 80-92),
+// kernel's allocation is sensitive to how its parameters arrive (a by-reference / by-value wrapper moved the 68 bytes of scratch it had
+// then to 80-92; 8 bytes since the MFMA film reduction),
 // and profiles, counters and docs keep the three-argument kernel name.  No include guard on purpose.
     static_assert(!STORE_T || !DIRECT, "STORE_T is a mode of the one-channel marches");
     constexpr int NCH = DIRECT ? 4 : 2;
@@ -52,13 +53,15 @@
         TraceOut tr, trs, trb;
         clear_trace(tr);
         int lit = 0;
-        float acc[NCH][2];
+        // film window of the item: win (primal of the one-channel integrators, film_reduce_mfma) or acc (film_accum_wave)
+        float acc[NCH][2], win[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) { acc[ch][0] = 0.f; acc[ch][1] = 0.f; }
         // A primal chunk of the one-channel integrators whose march is proven away (empty-space proof: every sample misses; hit
         // proof: every sample of the silhouette integrator hits) consists of its film weights: the sampler's offsets and the 5 x 5
         // window -- no camera ray, no box test, no re-projection (film_accum_offsets, dsdf_film.h).  Half of the listed chunks of
-        // the bench scene.
+        // the bench scene.  (Measured and rejected, DESIGN 5.59: such a pixel as ONE item -- the wave that draws its chunk 0 reduces all
+        // spp / 64 chunks and flushes once, the other tickets return at once: primal 12.57 -> 13.52 ms.)
         const bool proven = !DIFF && !DIRECT && !STORE_T && (known_hit || skip_trace);
         Lane L;
         if (STORE_T) {
@@ -88,7 +91,7 @@
         } else if (proven) {
             float r0, r1;
             sample_offsets(A, lane, r0, r1);
-            film_accum_offsets(r0, r1, true, known_hit ? 1.f : 0.f, wave_lds, lid, acc);
+            film_accum_offsets(r0, r1, known_hit ? 1.f : 0.f, wave_lds, lid, win);
             if (known_hit) tr.its_t = 0.f;                 // (statistics: the samples count as hits)
         } else {
         L = lane_setup<!DIFF>(A, P, lane, px, py);
@@ -125,10 +128,11 @@
         } else {
             // (primal: the sample lands where it was generated -- film_accum_offsets)
             const float val = shade_value(G, A, L, tr.its_t);
-            film_accum_offsets(L.r0, L.r1, true, val, wave_lds, lid, reinterpret_cast<float (*)[2]>(acc));
+            film_accum_offsets(L.r0, L.r1, val, wave_lds, lid, win);
         }
         }
-        if (!STORE_T) film_flush_wave<NCH>(block, A, px, py, lid, acc);
+        if (DIRECT || DIFF) { if (!STORE_T) film_flush_wave<NCH>(block, A, px, py, lid, acc); }
+        else if (!STORE_T) film_flush_mfma(block, A, px, py, lid, win);
         bool need = false;
         if (DIFF && !STORE_T) {
             need = needs_backward<DIRECT>(G, P, A, L, tr, lit);

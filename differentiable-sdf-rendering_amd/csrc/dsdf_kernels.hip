@@ -55,9 +55,9 @@ XfState g_xf_host = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0
 #define DSDF_BLOCK 256    /* threads per block of the general (any spp) render pass */
 #define DSDF_TSTRIDE 68   /* 64 + 4: rows 16-byte aligned, ds_read_b128 conflict-free across lanes */
 #define DSDF_TROWS 13     /* film transpose processes the 25 window slots in two chunks of <= 13 rows */
-#define DSDF_WAVE_LDS 1104 /* floats per wave: max(16 cache slots * 68 + 16 slot bases, 13 * 68) */
+#define DSDF_WAVE_LDS 1104 /* floats per wave: max(16 cache slots * 68 + 16 slot bases, 13 * 68 transpose rows, 15 * 68 MFMA film rows) */
 #ifndef DSDF_PRIMAL_MINWAVES
-#define DSDF_PRIMAL_MINWAVES 8   /* latency-bound: 64 VGPRs (a 52-byte spill) for 8 waves/SIMD measured 48.5 vs 52.3 ms */
+#define DSDF_PRIMAL_MINWAVES 8   /* latency-bound: 64 VGPRs (a 52-byte spill then, 8 bytes now) for 8 waves/SIMD measured 48.5 vs 52.3 ms */
 #endif
 
 struct AtomicAdd {
@@ -237,9 +237,10 @@ __device__ __forceinline__ void load_record(const float *r, size_t c, TraceOut &
 // Two kernels generate, trace, shade and splat the film samples (lane = pixel * spp + sample, reparam.py:140-155):
 //   k_render_items  spp % 64 == 0: every 64-lane wave sits in ONE pixel.  The pixels that survive the empty-space proof are
 //                   compacted into a work list (k_build_items) and traced by PERSISTENT single-wave workers: a wave takes the
-//                   next pixel with one atomic ticket, renders its spp / 64 chunks one after the other (cell cache for the
-//                   value-only march, per-lane gathers + tail hand-off for the differentiable one), reduces the film
-//                   contributions of ALL chunks across the wave and flushes the 5x5 window once.  (Round-2 PMC on the
+//                   next 64-sample CHUNK of a listed pixel with one atomic ticket (cell cache for the value-only march,
+//                   per-lane gathers for the differentiable one, the last rays of a wave handed to the tail queue), reduces
+//                   the chunk's film contributions across the wave -- the primal of the one-channel integrators as one MFMA
+//                   product, dsdf_film.h -- and flushes the 5x5 window of that chunk.  (Round-2 PMC on the
 //                   block-per-256-lanes predecessor: 71 % of the launched waves were empty, resident waves 5.9 / SIMD of 8 --
 //                   the LDS and the four wave slots of a block stayed allocated until its slowest wave had finished.)
 //   k_render_pass   any spp: one lane per sample in reference order, per-lane fetches and film atomics.

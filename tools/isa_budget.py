@@ -37,7 +37,7 @@ CLASSES = [   # regex on the demangled function name of an inline frame -> class
     (r'sampler_|sample_tea_32|pcg32_|sample_offsets', 'sampler (sample_tea_32 + PCG32)'),
     (r'camera_ray|bbox_ray_intersect|box_lo|box_hi|box_face_distance|closest_axis|lane_setup|lane_pixel|reproject', 'camera ray + box + re-projection'),
     (r'gauss_(f|exp|df)', 'film weights (Gaussian)'),
-    (r'film_accum_|film_flush_wave|splat_', 'film window: products, LDS transpose, reduce, flush'),
+    (r'film_accum_|film_reduce_mfma|film_flush_|splat_', 'film window: products, LDS transpose / MFMA product, reduce, flush'),
     (r'HandOffCtl|tail_reserve|tail_subq|xcc_id', 'tail hand-off'),
     (r'queue_unit|store_record|warp_weight_positive|view_queue', 'backward queue (weight test, compaction, records)'),
     (r'shade_value|direct_value', 'shading value'),
