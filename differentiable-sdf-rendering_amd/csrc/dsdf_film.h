@@ -202,44 +202,29 @@ __device__ __forceinline__ void tile_window_clear(const TileWindow &T, int lid) 
     wave_lds_sync();
 }
 
-// one sample: vals[NCH - 1] value channels + the weight channel (same statements as splat_lane / splat_lane_rgb)
+// one sample: vals[NCH - 1] value channels + the weight channel -- splat_lane<NCH - 1> with the adds going to the wave's window
 template <int NCH>
 __device__ __forceinline__ void tile_window_splat(const TileWindow &T, float *__restrict__ block, int Wb, int Hb, float u, float v,
                                                   const float *vals) {
-    const float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
-    const int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4];
+    const FilmTaps<false> F = film_taps<false>(u, v);
+    const bool inside = F.x0 >= T.x0 && F.x0 + 4 <= T.x0 + T.w && F.y0 >= T.y0 && F.y0 + 4 <= T.y0 + T.h;
+    film_taps_each(F, Wb, Hb, [=](int i, int j, size_t q) {
+        const float f = F.wx[i] * F.wy[j];
+        if (f == 0.f) return;
+        if (inside) {
+            float *dst = T.win + NCH * ((F.y0 + j - T.y0) * T.w + (F.x0 + i - T.x0));
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wx[i] = gauss_f((float)(x0 + i) - pfx);
-        wy[i] = gauss_f((float)(y0 + i) - pfy);
-    }
-    const bool inside = x0 >= T.x0 && x0 + 4 <= T.x0 + T.w && y0 >= T.y0 && y0 + 4 <= T.y0 + T.h;
+            for (int c = 0; c < NCH - 1; ++c)
+                if (vals[c] != 0.f) lds_add(dst + c, f * vals[c]);
+            lds_add(dst + (NCH - 1), f);
+        } else {        // (cannot happen for a sample of the tile; it would still be counted)
+            float *dst = block + NCH * q;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            const float f = wx[i] * wy[j];
-            if (f == 0.f) continue;
-            if (inside) {
-                float *dst = T.win + NCH * ((qy - T.y0) * T.w + (qx - T.x0));
-#pragma unroll
-                for (int c = 0; c < NCH - 1; ++c)
-                    if (vals[c] != 0.f) lds_add(dst + c, f * vals[c]);
-                lds_add(dst + (NCH - 1), f);
-            } else {        // (cannot happen for a sample of the tile; it would still be counted)
-                float *dst = block + NCH * ((size_t)qy * Wb + qx);
-#pragma unroll
-                for (int c = 0; c < NCH - 1; ++c)
-                    if (vals[c] != 0.f) atomicAdd(dst + c, f * vals[c]);
-                atomicAdd(dst + (NCH - 1), f);
-            }
+            for (int c = 0; c < NCH - 1; ++c)
+                if (vals[c] != 0.f) atomicAdd(dst + c, f * vals[c]);
+            atomicAdd(dst + (NCH - 1), f);
         }
-    }
+    });
 }
 
 template <int NCH>

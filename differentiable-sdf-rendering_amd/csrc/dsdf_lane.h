@@ -94,113 +94,72 @@ DSDF_HD float shade_value(const GridView &G, const ViewArgs &A, const Lane &L, f
     return fmaxf(dot(n, light_dir(A)), 0.f);
 }
 
-// ImageBlock::put for one lane: 4x4 window of the radius-2 Gaussian around
-// pos_f = uv + border - 0.5.  Internal film block has 2 channels (value, weight):
-// both integrators on the path emit R=G=B.
-template <class Adder>
-DSDF_HD void splat_lane(float *block, int Wb, int Hb, float u, float v, float val, Adder add) {
-    float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4];
+// ImageBlock::put for one lane: the footprint of the sample (film_taps, dsdf_math.h) into a film block of NV value channels + the
+// weight.  NV = 1: silhouette / simple shading, which emit R=G=B; 2: the (i, weight_sum, weight) block of the AOV debug render
+// (reparam.py:117-118: `block.put(position_sample, aovs + aovs_)`); 3: the (r,g,b,weight) block of sdf_direct_reparam.
+// Taps of weight zero and channels of value zero issue no add.  (The values go into the tap body BY VALUE: behind a reference the
+// compiler repeats the `!= 0` tests at every tap, k_render_pass<false, false> 2009 -> 2040 VALU; tile_window_splat captures by value too.)
+template <int NV, class Adder>
+DSDF_HD void splat_lane(float *block, int Wb, int Hb, float u, float v, const float *vals, Adder add) {
+    const FilmTaps<false> T = film_taps<false>(u, v);
+    float a[NV];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wx[i] = gauss_f((float)(x0 + i) - pfx);
-        wy[i] = gauss_f((float)(y0 + i) - pfy);
-    }
+    for (int c = 0; c < NV; ++c) a[c] = vals[c];
+    film_taps_each(T, Wb, Hb, [=](int i, int j, size_t q) {
+        float f = T.wx[i] * T.wy[j];
+        if (f == 0.f) return;
+        float *dst = block + (NV + 1) * q;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = wx[i] * wy[j];
-            if (f == 0.f) continue;
-            float *dst = block + 2 * ((size_t)qy * Wb + qx);
-            if (val != 0.f) add(dst, f * val);
-            add(dst + 1, f);
-        }
-    }
+        for (int c = 0; c < NV; ++c)
+            if (a[c] != 0.f) add(dst + c, f * a[c]);
+        add(dst + NV, f);
+    });
 }
 
-// Value channel only (the weight of the sample has been splatted already): tail rays, dsdf_tail.h.
+// The three blocks by name, as the kernels and the test harness call them: one value, the two AOVs, r g b.
 template <class Adder>
-DSDF_HD void splat_value_lane(float *block, int Wb, int Hb, float u, float v, float val, Adder add) {
-    float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-        float wy = gauss_f((float)qy - pfy);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = gauss_f((float)qx - pfx) * wy;
-            if (f != 0.f) add(block + 2 * ((size_t)qy * Wb + qx), f * val);
-        }
-    }
-}
-
-// The 3-channel (i, weight_sum, weight) block of the AOV debug render (reparam.py:117-118: `block.put(position_sample, aovs + aovs_)`).
+DSDF_HD void splat_lane(float *block, int Wb, int Hb, float u, float v, float val, Adder add) { splat_lane<1>(block, Wb, Hb, u, v, &val, add); }
 template <class Adder>
 DSDF_HD void splat_lane_aov(float *block, int Wb, int Hb, float u, float v, float a0, float a1, Adder add) {
-    float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wx[i] = gauss_f((float)(x0 + i) - pfx);
-        wy[i] = gauss_f((float)(y0 + i) - pfy);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = wx[i] * wy[j];
-            if (f == 0.f) continue;
-            float *dst = block + 3 * ((size_t)qy * Wb + qx);
-            if (a0 != 0.f) add(dst, f * a0);
-            if (a1 != 0.f) add(dst + 1, f * a1);
-            add(dst + 2, f);
-        }
-    }
+    const float aov[2] = {a0, a1};
+    splat_lane<2>(block, Wb, Hb, u, v, aov, add);
+}
+template <class Adder>
+DSDF_HD void splat_lane_rgb(float *block, int Wb, int Hb, float u, float v, const float *rgb, Adder add) { splat_lane<3>(block, Wb, Hb, u, v, rgb, add); }
+
+// Value channel only of the 2-channel block (the weight of the sample has been splatted already): tail rays, dsdf_tail.h.
+template <class Adder>
+DSDF_HD void splat_value_lane(float *block, int Wb, int Hb, float u, float v, float val, Adder add) {
+    const FilmTaps<false> T = film_taps<false>(u, v);
+    film_taps_each(T, Wb, Hb, [&](int i, int j, size_t q) {
+        float f = T.wx[i] * T.wy[j];
+        if (f != 0.f) add(block + 2 * q, f * val);
+    });
 }
 
-// Same for the 4-channel (r,g,b,weight) block of sdf_direct_reparam.
-template <class Adder>
-DSDF_HD void splat_lane_rgb(float *block, int Wb, int Hb, float u, float v, const float rgb[3], Adder add) {
-    float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4];
+// Film adjoint gather of one sample, the transpose of splat_lane<NV>: ImageBlock::put is linear in the values and differentiable
+// in the position through the filter weights.  block_adj: adjoint of the (NV + 1)-channel film block; vals: the sample's values.
+//   a_c[c] = sum f Bbar_c,  a_w = sum f Bbar_W,  u_bar / v_bar = sum (sum_c Bbar_c vals_c + Bbar_W) d f / d(u, v)     (a_W = 1)
+template <int NV> struct FilmAdjoint { float a_c[NV], a_w, u_bar, v_bar; };
+
+template <int NV>
+DSDF_HD FilmAdjoint<NV> film_gather(const float *block_adj, int Wb, int Hb, float u, float v, const float *vals) {
+    FilmAdjoint<NV> a;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wx[i] = gauss_f((float)(x0 + i) - pfx);
-        wy[i] = gauss_f((float)(y0 + i) - pfy);
-    }
+    for (int c = 0; c < NV; ++c) a.a_c[c] = 0.f;
+    a.a_w = 0.f; a.u_bar = 0.f; a.v_bar = 0.f;
+    const FilmTaps<true> T = film_taps<true>(u, v);
+    film_taps_each(T, Wb, Hb, [&](int i, int j, size_t q) {
+        const float *ba = block_adj + (NV + 1) * q;
+        float f = T.wx[i] * T.wy[j];
+        float s = ba[NV];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = wx[i] * wy[j];
-            if (f == 0.f) continue;
-            float *dst = block + 4 * ((size_t)qy * Wb + qx);
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                if (rgb[c] != 0.f) add(dst + c, f * rgb[c]);
-            add(dst + 3, f);
-        }
-    }
+        for (int c = 0; c < NV; ++c) { a.a_c[c] = fmaf(f, ba[c], a.a_c[c]); s = fmaf(ba[c], vals[c], s); }
+        a.a_w = fmaf(f, ba[NV], a.a_w);
+        a.u_bar = fmaf(s, -T.dwx[i] * T.wy[j], a.u_bar);   // d f / d u = -F'(rel_x) F(rel_y)
+        a.v_bar = fmaf(s, -T.wx[i] * T.dwy[j], a.v_bar);
+    });
+    return a;
 }
 
 // ---------------------------------------------------------------------------
@@ -214,7 +173,9 @@ DSDF_HD void splat_lane_rgb(float *block, int Wb, int Hb, float u, float v, cons
 // d p_hit = t d dir + d dt,  dG = dg_0 + H d p_hit,  d val = [n.l > 0] l . (I - n n^T) dG / |G|.
 // Outputs: tangents of the sample's value / weight channel entries and of its film position.
 // ---------------------------------------------------------------------------
-struct SampleTangent { float val, d_val, d_w, d_u, d_v, u, v; };
+template <int NV> struct SampleTangentN { float val[NV], d_val[NV], d_w, d_u, d_v, u, v; };   // NV value channels:
+using SampleTangent = SampleTangentN<1>;                                                       // silhouette / simple shading
+using SampleTangentRgb = SampleTangentN<3>;                                                    // sdf_direct_reparam
 
 DSDF_HD bool lane_forward_tangent(const GridView &G, const float *tangent, V3 dp, const dsdf_params &P, const ViewArgs &A,
                                   const Lane &L, const TraceOut &tr, SampleTangent &out) {
@@ -223,7 +184,7 @@ DSDF_HD bool lane_forward_tangent(const GridView &G, const float *tangent, V3 dp
     const GridView T = view_of(G, tangent);
     Reproj rp = reproject(A.cam, P, o + d, A.W, A.H);
     out.u = rp.u; out.v = rp.v;
-    out.val = 0.f; out.d_val = 0.f; out.d_w = 0.f; out.d_u = 0.f; out.d_v = 0.f;
+    out.val[0] = 0.f; out.d_val[0] = 0.f; out.d_w = 0.f; out.d_u = 0.f; out.d_v = 0.f;
     V3 d_dir = mk(0.f, 0.f, 0.f);
     float d_div = 0.f;
     bool did = false;
@@ -240,7 +201,7 @@ DSDF_HD bool lane_forward_tangent(const GridView &G, const float *tangent, V3 dp
         }
     }
     if (hit) {
-        if (A.integrator == DSDF_SILHOUETTE) out.val = 1.f;
+        if (A.integrator == DSDF_SILHOUETTE) out.val[0] = 1.f;
         else {
             const V3 phit = fma3(tr.its_t, d, o);
             float vhit; V3 ghit; float Hhit[6];
@@ -249,61 +210,44 @@ DSDF_HD bool lane_forward_tangent(const GridView &G, const float *tangent, V3 dp
             const V3 n = ghit * (1.f / gl);
             const V3 l = light_dir(A);
             const float ndl = dot(n, l);
-            out.val = fmaxf(ndl, 0.f);
+            out.val[0] = fmaxf(ndl, 0.f);
             float tv = 0.f; V3 tg = mk(0.f, 0.f, 0.f); float tH[6];
             if (tangent) eval_cubic<1>(T, phit, tv, tg, tH);
             const float dv0 = tv - dot(ghit, dp) + tr.its_t * dot(ghit, d_dir);
             const float dt = dv0 / dot(ghit, -d);
             const V3 dpos = tr.its_t * d_dir + dt * d;
             const V3 dG = tg - symmul(Hhit, dp) + symmul(Hhit, dpos);
-            if (ndl > 0.f) out.d_val = (dot(l, dG) - ndl * dot(n, dG)) / gl;
+            if (ndl > 0.f) out.d_val[0] = (dot(l, dG) - ndl * dot(n, dG)) / gl;
             did = true;
         }
     }
     // a_v = val * div * rw, a_w = div * rw (div, rw have value 1); film position through the attached direction
-    const V3 dref = mk(A.cam.left[0] * d_dir.x + A.cam.left[1] * d_dir.y + A.cam.left[2] * d_dir.z,
-                       A.cam.up[0] * d_dir.x + A.cam.up[1] * d_dir.y + A.cam.up[2] * d_dir.z,
-                       A.cam.dir[0] * d_dir.x + A.cam.dir[1] * d_dir.y + A.cam.dir[2] * d_dir.z);
-    const float iz = 1.f / rp.ref.z;
-    const float ku = -0.5f * (float)A.W / A.cam.tan_half_fov;
-    out.d_u = ku * iz * (dref.x - rp.ref.x * iz * dref.z);
-    out.d_v = ku * iz * (dref.y - rp.ref.y * iz * dref.z);
-    float d_rw = 0.f;
-    if (rp.inside) d_rw = dot(rp.ref, dref) / (rp.dist * rp.dist) - 3.f * iz * dref.z;
+    float d_rw;
+    reproject_tangent(A.cam, A.W, rp, d_dir, out.d_u, out.d_v, d_rw);
     out.d_w = d_div + d_rw;
-    out.d_val = out.d_val + out.val * out.d_w;
+    out.d_val[0] = out.d_val[0] + out.val[0] * out.d_w;
     return did;
 }
 
-// splat of a sample tangent into the tangent film block (value, weight): d(f a) = f da + a (f_u du + f_v dv)
-template <class Adder>
-DSDF_HD void splat_tangent(float *dblock, int Wb, int Hb, const SampleTangent &s, Adder add) {
-    float pfx = s.u + (DSDF_BORDER - 0.5f), pfy = s.v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4], dwx[4], dwy[4];
+// splat of a sample tangent into the tangent film block (NV values, weight): d(f a) = f da + a (f_u du + f_v dv)
+template <int NV, class Adder>
+DSDF_HD void splat_tangent(float *dblock, int Wb, int Hb, const SampleTangentN<NV> &s, Adder add) {
+    const FilmTaps<true> T = film_taps<true>(s.u, s.v);
+    film_taps_each(T, Wb, Hb, [&](int i, int j, size_t q) {
+        float f = T.wx[i] * T.wy[j];
+        float dfp = -T.dwx[i] * T.wy[j] * s.d_u - T.wx[i] * T.dwy[j] * s.d_v;     // d f / d(u,v) . (du, dv)
+        float *dst = dblock + (NV + 1) * q;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float rx = (float)(x0 + i) - pfx, ry = (float)(y0 + i) - pfy;
-        wx[i] = gauss_f(rx); dwx[i] = gauss_df(rx);
-        wy[i] = gauss_f(ry); dwy[i] = gauss_df(ry);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = wx[i] * wy[j];
-            float dfp = -dwx[i] * wy[j] * s.d_u - wx[i] * dwy[j] * s.d_v;     // d f / d(u,v) . (du, dv)
-            float tv = f * s.d_val + s.val * dfp, tw = f * s.d_w + dfp;
-            float *dst = dblock + 2 * ((size_t)qy * Wb + qx);
-            if (tv != 0.f) add(dst, tv);
-            if (tw != 0.f) add(dst + 1, tw);
+        for (int c = 0; c < NV; ++c) {
+            float tv = f * s.d_val[c] + s.val[c] * dfp;
+            if (tv != 0.f) add(dst + c, tv);
         }
-    }
+        float tw = f * s.d_w + dfp;
+        if (tw != 0.f) add(dst + NV, tw);
+    });
 }
+template <class Adder>
+DSDF_HD void splat_tangent_rgb(float *dblock, int Wb, int Hb, const SampleTangentRgb &s, Adder add) { splat_tangent(dblock, Wb, Hb, s, add); }
 
 // ---------------------------------------------------------------------------
 // sdf_direct_reparam.sample() (integrators/sdf_direct_reparam.py:16-75, use_mis = False): emitter sampling of a
@@ -580,11 +524,7 @@ DSDF_HD bool lane_backward(const GridView &G, const dsdf_params &P, const ViewAr
     req[0].on = false; req[1].on = false;
     const V3 o = L.ray.o, d = L.ray.d;
     bool hit = tr.its_t < INFINITY;
-    // --- film adjoint gather (ImageBlock::put is linear in the values and
-    //     differentiable in the position through the filter weights)
     Reproj rp = reproject(A.cam, P, o + d, A.W, A.H);
-    float pfx = rp.u + (DSDF_BORDER - 0.5f), pfy = rp.v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
     float val = 0.f;
     V3 ghit = mk(0.f, 0.f, 0.f); float Hhit[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; float vhit = 0.f;
     V3 phit = o;
@@ -597,51 +537,12 @@ DSDF_HD bool lane_backward(const GridView &G, const dsdf_params &P, const ViewAr
             val = fmaxf(dot(ghit, light_dir(A)) / gl, 0.f);
         }
     }
-    float a_val = 0.f, a_w = 0.f, u_bar = 0.f, v_bar = 0.f;
-    float wx[4], wy[4], dwx[4], dwy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float rx = (float)(x0 + i) - pfx, ry = (float)(y0 + i) - pfy;
-        wx[i] = gauss_f(rx); dwx[i] = gauss_df(rx);
-        wy[i] = gauss_f(ry); dwy[i] = gauss_df(ry);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= A.Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= A.Wb) continue;
-            const float *ba = block_adj + 2 * ((size_t)qy * A.Wb + qx);
-            float bs = ba[0], bw = ba[1];
-            float f = wx[i] * wy[j];
-            a_val = fmaf(f, bs, a_val);
-            a_w = fmaf(f, bw, a_w);
-            float s = bs * val + bw;                 // sum_c Bbar_c * a_c  (a_W = 1)
-            u_bar = fmaf(s, -dwx[i] * wy[j], u_bar); // d f / d u = -F'(rel_x) F(rel_y)
-            v_bar = fmaf(s, -wx[i] * dwy[j], v_bar);
-        }
-    }
+    const FilmAdjoint<1> fa = film_gather<1>(block_adj, A.Wb, A.Hb, rp.u, rp.v, &val);
+    const float a_val = fa.a_c[0];
     // a_c = val * div * rw (c = value channel), a_W = div * rw; div, rw have value 1
-    float div_bar = val * a_val + a_w;
-    float rw_bar = rp.inside ? div_bar : 0.f;        // reparam.py:103 (select(rw>0, rw/detach(rw), 1))
+    float div_bar = val * a_val + fa.a_w;
     // --- adjoint of the warped direction d' (value d): through uv and log importance
-    V3 dir_bar = mk(0.f, 0.f, 0.f);
-    {
-        float cot = 1.f / A.cam.tan_half_fov;
-        float iz = 1.f / rp.ref.z;
-        // u = W (0.5 - 0.5 cot x/z), v = H (0.5 - 0.5 aspect cot y/z), H*aspect = W
-        float ku = -0.5f * (float)A.W * cot, kv = ku;
-        V3 ref_bar = mk(u_bar * ku * iz, v_bar * kv * iz,
-                        -(u_bar * ku * rp.ref.x + v_bar * kv * rp.ref.y) * iz * iz);
-        // log rw = log dist - 3 log z
-        float id2 = 1.f / (rp.dist * rp.dist);
-        ref_bar = ref_bar + rw_bar * mk(rp.ref.x * id2, rp.ref.y * id2, rp.ref.z * id2 - 3.f * iz);
-        dir_bar = mk(A.cam.left[0] * ref_bar.x + A.cam.up[0] * ref_bar.y + A.cam.dir[0] * ref_bar.z,
-                     A.cam.left[1] * ref_bar.x + A.cam.up[1] * ref_bar.y + A.cam.dir[1] * ref_bar.z,
-                     A.cam.left[2] * ref_bar.x + A.cam.up[2] * ref_bar.y + A.cam.dir[2] * ref_bar.z);
-    }
+    V3 dir_bar = reproject_adjoint(A.cam, A.W, rp, fa.u_bar, fa.v_bar, div_bar);
     bool did = false;
     // --- shading channel (shapes.py:347-366): t = replace_grad(t, v(p)/c), n = normalize(grad(p))
     if (hit && A.integrator == DSDF_SIMPLE_SHADING) {
@@ -693,8 +594,6 @@ DSDF_HD bool lane_backward_direct(const GridView &G, const dsdf_params &P, const
     const V3 o = L.ray.o, d = L.ray.d;
     const bool hit = tr.its_t < INFINITY;
     Reproj rp = reproject(A.cam, P, o + d, A.W, A.H);
-    float pfx = rp.u + (DSDF_BORDER - 0.5f), pfy = rp.v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
     float rgb[3] = {0.f, 0.f, 0.f}, rgb_e[3] = {0.f, 0.f, 0.f}, rgb_b[3] = {0.f, 0.f, 0.f};
     DirectHit h;
     BsdfRay br;
@@ -737,48 +636,11 @@ DSDF_HD bool lane_backward_direct(const GridView &G, const dsdf_params &P, const
 #endif
         }
     }
-    float a_c[3] = {0.f, 0.f, 0.f}, a_w = 0.f, u_bar = 0.f, v_bar = 0.f;
-    float wx[4], wy[4], dwx[4], dwy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float rx = (float)(x0 + i) - pfx, ry = (float)(y0 + i) - pfy;
-        wx[i] = gauss_f(rx); dwx[i] = gauss_df(rx);
-        wy[i] = gauss_f(ry); dwy[i] = gauss_df(ry);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= A.Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= A.Wb) continue;
-            const float *ba = block_adj + 4 * ((size_t)qy * A.Wb + qx);
-            float f = wx[i] * wy[j];
-            float s = ba[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { a_c[c] = fmaf(f, ba[c], a_c[c]); s = fmaf(ba[c], rgb[c], s); }
-            a_w = fmaf(f, ba[3], a_w);
-            u_bar = fmaf(s, -dwx[i] * wy[j], u_bar);
-            v_bar = fmaf(s, -wx[i] * dwy[j], v_bar);
-        }
-    }
+    const FilmAdjoint<3> fa = film_gather<3>(block_adj, A.Wb, A.Hb, rp.u, rp.v, rgb);
+    const float *a_c = fa.a_c;
     const float rgb_dot = rgb[0] * a_c[0] + rgb[1] * a_c[1] + rgb[2] * a_c[2];
-    float div_bar = rgb_dot + a_w;
-    float rw_bar = rp.inside ? div_bar : 0.f;
-    V3 dir_bar = mk(0.f, 0.f, 0.f);
-    {
-        float cot = 1.f / A.cam.tan_half_fov;
-        float iz = 1.f / rp.ref.z;
-        float ku = -0.5f * (float)A.W * cot, kv = ku;
-        V3 ref_bar = mk(u_bar * ku * iz, v_bar * kv * iz,
-                        -(u_bar * ku * rp.ref.x + v_bar * kv * rp.ref.y) * iz * iz);
-        float id2 = 1.f / (rp.dist * rp.dist);
-        ref_bar = ref_bar + rw_bar * mk(rp.ref.x * id2, rp.ref.y * id2, rp.ref.z * id2 - 3.f * iz);
-        dir_bar = mk(A.cam.left[0] * ref_bar.x + A.cam.up[0] * ref_bar.y + A.cam.dir[0] * ref_bar.z,
-                     A.cam.left[1] * ref_bar.x + A.cam.up[1] * ref_bar.y + A.cam.dir[1] * ref_bar.z,
-                     A.cam.left[2] * ref_bar.x + A.cam.up[2] * ref_bar.y + A.cam.dir[2] * ref_bar.z);
-    }
+    float div_bar = rgb_dot + fa.a_w;
+    V3 dir_bar = reproject_adjoint(A.cam, A.W, rp, fa.u_bar, fa.v_bar, div_bar);
     bool did = false;
     if (lit) {
         float vhit; V3 ghit; float Hhit[6];
@@ -927,48 +789,11 @@ DSDF_HD bool lane_backward_apply(const dsdf_params &P, const ViewArgs &A, const 
     if (!c.flags) return false;
     const V3 o = L.ray.o, d = L.ray.d;
     Reproj rp = reproject(A.cam, P, o + d, A.W, A.H);
-    float pfx = rp.u + (DSDF_BORDER - 0.5f), pfy = rp.v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
     const float val = c.val;
-    float a_val = 0.f, a_w = 0.f, u_bar = 0.f, v_bar = 0.f;
-    float wx[4], wy[4], dwx[4], dwy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float rx = (float)(x0 + i) - pfx, ry = (float)(y0 + i) - pfy;
-        wx[i] = gauss_f(rx); dwx[i] = gauss_df(rx);
-        wy[i] = gauss_f(ry); dwy[i] = gauss_df(ry);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= A.Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= A.Wb) continue;
-            const float *ba = block_adj + 2 * ((size_t)qy * A.Wb + qx);
-            float bs = ba[0], bw = ba[1];
-            float f = wx[i] * wy[j];
-            a_val = fmaf(f, bs, a_val);
-            a_w = fmaf(f, bw, a_w);
-            float s = bs * val + bw;
-            u_bar = fmaf(s, -dwx[i] * wy[j], u_bar);
-            v_bar = fmaf(s, -wx[i] * dwy[j], v_bar);
-        }
-    }
-    const float div_bar = val * a_val + a_w;
-    const float rw_bar = rp.inside ? div_bar : 0.f;
-    V3 dir_bar;
-    {
-        const float cot = 1.f / A.cam.tan_half_fov, iz = 1.f / rp.ref.z;
-        const float ku = -0.5f * (float)A.W * cot, kv = ku;
-        V3 ref_bar = mk(u_bar * ku * iz, v_bar * kv * iz, -(u_bar * ku * rp.ref.x + v_bar * kv * rp.ref.y) * iz * iz);
-        const float id2 = 1.f / (rp.dist * rp.dist);
-        ref_bar = ref_bar + rw_bar * mk(rp.ref.x * id2, rp.ref.y * id2, rp.ref.z * id2 - 3.f * iz);
-        dir_bar = mk(A.cam.left[0] * ref_bar.x + A.cam.up[0] * ref_bar.y + A.cam.dir[0] * ref_bar.z,
-                     A.cam.left[1] * ref_bar.x + A.cam.up[1] * ref_bar.y + A.cam.dir[1] * ref_bar.z,
-                     A.cam.left[2] * ref_bar.x + A.cam.up[2] * ref_bar.y + A.cam.dir[2] * ref_bar.z);
-    }
+    const FilmAdjoint<1> fa = film_gather<1>(block_adj, A.Wb, A.Hb, rp.u, rp.v, &val);
+    const float a_val = fa.a_c[0];
+    const float div_bar = val * a_val + fa.a_w;
+    V3 dir_bar = reproject_adjoint(A.cam, A.W, rp, fa.u_bar, fa.v_bar, div_bar);
     if (c.flags & 2u) {
         dir_bar = dir_bar + a_val * c.W;
         req[1].on = true; req[1].x = fma3(tr.its_t, d, o); req[1].cv = a_val * c.k0; req[1].cg = a_val * c.U;
@@ -994,8 +819,6 @@ DSDF_HD bool lane_backward_apply(const dsdf_params &P, const ViewArgs &A, const 
 //   radiance          d rgb_c = env_c (ke + kb) grad a_c . d p + a_c env_c 4 w_e (dn . d_s + n . d d_s') + rgb_e,c d det_e + rgb_b,c d det_b
 // Outputs: tangents of the sample's three value channel entries, of its weight entry and of its film position.
 // ---------------------------------------------------------------------------
-struct SampleTangentRgb { float val[3], d_val[3], d_w, d_u, d_v, u, v; };
-
 DSDF_HD void tangent_lookup(const GridView &G, const GridView &T, bool has_t, V3 x, V3 g, const float H[6], V3 dp, V3 dx, float &dv, V3 &dg) {
     float tv = 0.f; V3 tg = mk(0.f, 0.f, 0.f); float tH[6];
     if (has_t) eval_cubic<1>(T, x, tv, tg, tH);
@@ -1099,53 +922,12 @@ DSDF_HD bool lane_forward_tangent_direct(const GridView &G, const float *tangent
             did = true;
         }
     }
-    const V3 dref = mk(A.cam.left[0] * d_dir.x + A.cam.left[1] * d_dir.y + A.cam.left[2] * d_dir.z,
-                       A.cam.up[0] * d_dir.x + A.cam.up[1] * d_dir.y + A.cam.up[2] * d_dir.z,
-                       A.cam.dir[0] * d_dir.x + A.cam.dir[1] * d_dir.y + A.cam.dir[2] * d_dir.z);
-    const float iz = 1.f / rp.ref.z;
-    const float ku = -0.5f * (float)A.W / A.cam.tan_half_fov;
-    out.d_u = ku * iz * (dref.x - rp.ref.x * iz * dref.z);
-    out.d_v = ku * iz * (dref.y - rp.ref.y * iz * dref.z);
-    float d_rw = 0.f;
-    if (rp.inside) d_rw = dot(rp.ref, dref) / (rp.dist * rp.dist) - 3.f * iz * dref.z;
+    float d_rw;
+    reproject_tangent(A.cam, A.W, rp, d_dir, out.d_u, out.d_v, d_rw);
     out.d_w = d_div + d_rw;
 #pragma unroll
     for (int c = 0; c < 3; ++c) out.d_val[c] = out.d_val[c] + out.val[c] * out.d_w;
     return did;
-}
-
-// splat of a sample tangent into the 4-channel tangent film block
-template <class Adder>
-DSDF_HD void splat_tangent_rgb(float *dblock, int Wb, int Hb, const SampleTangentRgb &s, Adder add) {
-    float pfx = s.u + (DSDF_BORDER - 0.5f), pfy = s.v + (DSDF_BORDER - 0.5f);
-    int x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS), y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
-    float wx[4], wy[4], dwx[4], dwy[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float rx = (float)(x0 + i) - pfx, ry = (float)(y0 + i) - pfy;
-        wx[i] = gauss_f(rx); dwx[i] = gauss_df(rx);
-        wy[i] = gauss_f(ry); dwy[i] = gauss_df(ry);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int qy = y0 + j;
-        if (qy < 0 || qy >= Hb) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int qx = x0 + i;
-            if (qx < 0 || qx >= Wb) continue;
-            float f = wx[i] * wy[j];
-            float dfp = -dwx[i] * wy[j] * s.d_u - wx[i] * dwy[j] * s.d_v;
-            float *dst = dblock + 4 * ((size_t)qy * Wb + qx);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float tv = f * s.d_val[c] + s.val[c] * dfp;
-                if (tv != 0.f) add(dst + c, tv);
-            }
-            float tw = f * s.d_w + dfp;
-            if (tw != 0.f) add(dst + 3, tw);
-        }
-    }
 }
 
 // Does a gradient-pass sample go to the backward queue?  It does when its warp term can be non-zero or when its value depends on the

@@ -949,6 +949,37 @@ DSDF_HD Reproj reproject(const dsdf_camera &c, const dsdf_params &P, V3 p, int W
     return r;
 }
 
+// Adjoint of `reproject` in the point (= the warped direction d', value d): from the adjoints of the film position (u, v) and of
+// the log importance to dir_bar, through ref_bar and the camera frame.
+//   u = W (0.5 - 0.5 cot x/z), v = H (0.5 - 0.5 aspect cot y/z), H*aspect = W;   log rw = log dist - 3 log z
+// rw_bar reaches the direction only where the importance is non-zero (reparam.py:103: select(rw>0, rw/detach(rw), 1)).
+DSDF_HD V3 reproject_adjoint(const dsdf_camera &c, int W, const Reproj &rp, float u_bar, float v_bar, float rw_bar) {
+    if (!rp.inside) rw_bar = 0.f;
+    float cot = 1.f / c.tan_half_fov;
+    float iz = 1.f / rp.ref.z;
+    float ku = -0.5f * (float)W * cot, kv = ku;
+    V3 ref_bar = mk(u_bar * ku * iz, v_bar * kv * iz,
+                    -(u_bar * ku * rp.ref.x + v_bar * kv * rp.ref.y) * iz * iz);
+    float id2 = 1.f / (rp.dist * rp.dist);
+    ref_bar = ref_bar + rw_bar * mk(rp.ref.x * id2, rp.ref.y * id2, rp.ref.z * id2 - 3.f * iz);
+    return mk(c.left[0] * ref_bar.x + c.up[0] * ref_bar.y + c.dir[0] * ref_bar.z,
+              c.left[1] * ref_bar.x + c.up[1] * ref_bar.y + c.dir[1] * ref_bar.z,
+              c.left[2] * ref_bar.x + c.up[2] * ref_bar.y + c.dir[2] * ref_bar.z);
+}
+
+// Its transpose (forward mode): the tangent d_dir of the direction to the tangents of the film position and of the log importance.
+DSDF_HD void reproject_tangent(const dsdf_camera &c, int W, const Reproj &rp, V3 d_dir, float &d_u, float &d_v, float &d_rw) {
+    const V3 dref = mk(c.left[0] * d_dir.x + c.left[1] * d_dir.y + c.left[2] * d_dir.z,
+                       c.up[0] * d_dir.x + c.up[1] * d_dir.y + c.up[2] * d_dir.z,
+                       c.dir[0] * d_dir.x + c.dir[1] * d_dir.y + c.dir[2] * d_dir.z);
+    const float iz = 1.f / rp.ref.z;
+    const float ku = -0.5f * (float)W / c.tan_half_fov;
+    d_u = ku * iz * (dref.x - rp.ref.x * iz * dref.z);
+    d_v = ku * iz * (dref.y - rp.ref.y * iz * dref.z);
+    d_rw = 0.f;
+    if (rp.inside) d_rw = dot(rp.ref, dref) / (rp.dist * rp.dist) - 3.f * iz * dref.z;
+}
+
 #define DSDF_BORDER 2
 #define DSDF_FILTER_RADIUS 2.0f
 #define DSDF_FILTER_ALPHA (-2.0f)            /* -1/(2*0.5^2) */
@@ -966,6 +997,42 @@ DSDF_HD float gauss_f(float x) { return fmaxf(0.f, gauss_exp(x) - DSDF_FILTER_BI
 DSDF_HD float gauss_df(float x) {
     float e = gauss_exp(x);
     return (e - DSDF_FILTER_BIAS) > 0.f ? 2.f * DSDF_FILTER_ALPHA * x * e : 0.f;
+}
+
+// The footprint of one sample on the film block (ImageBlock::put): the 4x4 pixels around pos_f = uv + border - 0.5 that the
+// radius-2 Gaussian reaches, x0 = ceil(pos_f - radius), with the separable weights F(rel) per axis -- and, with D, their derivatives
+// F'(rel): d f / d u = -F'(rel_x) F(rel_y), d f / d v = -F(rel_x) F'(rel_y).  Every per-sample splat and gather of the film is written
+// on these two functions; only the wave-level 5x5 windows centred on a pixel (dsdf_film.h) have a form of their own.
+template <bool D> struct FilmTaps { int x0, y0; float wx[4], wy[4], dwx[D ? 4 : 1], dwy[D ? 4 : 1]; };
+
+template <bool D>
+DSDF_HD FilmTaps<D> film_taps(float u, float v) {
+    FilmTaps<D> T;
+    float pfx = u + (DSDF_BORDER - 0.5f), pfy = v + (DSDF_BORDER - 0.5f);
+    T.x0 = (int)ceilf(pfx - DSDF_FILTER_RADIUS); T.y0 = (int)ceilf(pfy - DSDF_FILTER_RADIUS);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float rx = (float)(T.x0 + i) - pfx, ry = (float)(T.y0 + i) - pfy;
+        T.wx[i] = gauss_f(rx); T.wy[i] = gauss_f(ry);
+        if (D) { T.dwx[i] = gauss_df(rx); T.dwy[i] = gauss_df(ry); }
+    }
+    return T;
+}
+
+// body(i, j, pixel) for the taps (i, j) of the footprint that lie inside the Wb x Hb block; pixel = qy * Wb + qx
+template <bool D, class Body>
+DSDF_HD void film_taps_each(const FilmTaps<D> &T, int Wb, int Hb, Body body) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int qy = T.y0 + j;
+        if (qy < 0 || qy >= Hb) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int qx = T.x0 + i;
+            if (qx < 0 || qx >= Wb) continue;
+            body(i, j, (size_t)qy * Wb + qx);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------

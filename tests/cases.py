@@ -17,6 +17,8 @@ def make_case(name):
         'blob32_spp192': (lambda: O.blob_grid(32, n=6, seed=1), 3, 2, 6, 6, 192, 5),
         # 2 spp: 8 x 4 pixel-tile waves of the general pass, film window in LDS, ragged tiles at the right / bottom edge
         'blob32_spp2': (lambda: O.blob_grid(32, n=6, seed=1), 3, 2, 21, 13, 2, 6),
+        # 3 spp: neither a power of two nor a multiple of 64 -- the general pass in LINEAR lane order, every sample splatted on its own
+        'blob32_spp3': (lambda: O.blob_grid(32, n=6, seed=1), 3, 1, 24, 24, 3, 8),
     }[name]
     gridfn, ncam, icam, W, H, spp, seed = cfg
     gen = torch.Generator().manual_seed(seed)

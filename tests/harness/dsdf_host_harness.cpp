@@ -632,4 +632,31 @@ int hh_tail_hop(int first, int k) { return (int)tail_hop((uint32_t)first, (uint3
 int hh_item_of(int share, int j) { return (int)item_of((uint32_t)share, (uint32_t)j); }
 int hh_item_seg() { return (int)DSDF_ITEM_SEG; }
 
+// The film footprint (csrc/dsdf_math.h: film_taps<true>, film_taps_each) of n film positions uv on a Wb x Hb block: x0y0[2 n],
+// w[16 n] = wx, wy, dwx, dwy and pix[16 n] = the pixel index film_taps_each passes for tap (i, j) at [4 j + i], -1 for a clipped tap.
+void hh_film_taps(long n, const float *uv, int Wb, int Hb, int *x0y0, float *w, int *pix) {
+    for (long k = 0; k < n; ++k) {
+        const FilmTaps<true> T = film_taps<true>(uv[2 * k], uv[2 * k + 1]);
+        x0y0[2 * k] = T.x0; x0y0[2 * k + 1] = T.y0;
+        for (int i = 0; i < 4; ++i) {
+            w[16 * k + i] = T.wx[i]; w[16 * k + 4 + i] = T.wy[i]; w[16 * k + 8 + i] = T.dwx[i]; w[16 * k + 12 + i] = T.dwy[i];
+        }
+        for (int t = 0; t < 16; ++t) pix[16 * k + t] = -1;
+        film_taps_each(T, Wb, Hb, [&](int i, int j, size_t q) { pix[16 * k + 4 * j + i] = (int)q; });
+    }
+}
+
+// reproject_adjoint and reproject_tangent (csrc/dsdf_math.h) at n points p: bars[3 n] = (u_bar, v_bar, rw_bar) -> dir_bar[3 n];
+// d_dir[3 n] -> duvw[3 n] = (d_u, d_v, d_rw); inside[n] = Reproj::inside.
+void hh_reproject_pair(const dsdf_camera *cam, const dsdf_params *prm, int W, int H, long n, const float *p, const float *bars,
+                       const float *d_dir, float *dir_bar, float *duvw, int *inside) {
+    for (long k = 0; k < n; ++k) {
+        const Reproj rp = reproject(*cam, *prm, mk(p[3 * k], p[3 * k + 1], p[3 * k + 2]), W, H);
+        const V3 db = reproject_adjoint(*cam, W, rp, bars[3 * k], bars[3 * k + 1], bars[3 * k + 2]);
+        dir_bar[3 * k] = db.x; dir_bar[3 * k + 1] = db.y; dir_bar[3 * k + 2] = db.z;
+        reproject_tangent(*cam, W, rp, mk(d_dir[3 * k], d_dir[3 * k + 1], d_dir[3 * k + 2]), duvw[3 * k], duvw[3 * k + 1], duvw[3 * k + 2]);
+        inside[k] = rp.inside ? 1 : 0;
+    }
+}
+
 }  // extern "C"

@@ -30,7 +30,7 @@ def setup(dsdf, case, ex, hide=False):
     return grid, sen, sh
 
 
-@pytest.mark.parametrize('name', ['sphere16', 'blob32', 'blob32_spp64', 'blob48_rect'])
+@pytest.mark.parametrize('name', ['sphere16', 'blob32', 'blob32_spp64', 'blob48_rect', 'blob32_spp3'])
 @pytest.mark.parametrize('hide', [False, True])
 def test_direct_forward_gpu(dsdf, name, hide):
     case = make_case(name)
@@ -43,7 +43,7 @@ def test_direct_forward_gpu(dsdf, name, hide):
         assert rel_l2(img.cpu(), ref) < FWD_TOL
 
 
-@pytest.mark.parametrize('name', ['sphere16', 'blob32', 'blob32_spp64', 'blob48_rect'])
+@pytest.mark.parametrize('name', ['sphere16', 'blob32', 'blob32_spp64', 'blob48_rect', 'blob32_spp3'])
 @pytest.mark.parametrize('reparam', [True, False])
 def test_direct_backward_gpu(dsdf, name, reparam):
     case = make_case(name)

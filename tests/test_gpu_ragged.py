@@ -205,6 +205,7 @@ def test_proofs_exact_on_ragged_grids_fine_film(dsdf, name, W, H):
 
 
 # ------------------------------------------------------------------ gradient pass
+SWEEP_TAILS = {}                # (case, integrator, reparam) -> rays the gradient sweep handed to the tail kernel
 @pytest.mark.parametrize('name', NAMES)
 @pytest.mark.parametrize('integ,reparam', [(O.SILHOUETTE, True), (O.SILHOUETTE, False), (O.SIMPLE_SHADING, True)])
 def test_gradient_pass_ragged(dsdf, name, integ, reparam):
@@ -219,9 +220,12 @@ def test_gradient_pass_ragged(dsdf, name, integ, reparam):
     case = ragged_case(name, walls=False)
     grid = _grid(dsdf, case)
     fails = []
+    tails = 0
     for v, sen in zip(case['views'], _sensors(dsdf, case)):
+        st = dsdf.new_stats('cuda')
         gg, img = dsdf.render_backward(grid, sen, v['spp'], v['grad_image'].cuda()[None], offsets=v['offsets'].cuda(), integrator=integ,
-                                       reparam=reparam, return_image=True)
+                                       reparam=reparam, return_image=True, stats=st)
+        tails += dsdf.stats_dict(st)['tail_rays']
         gg = gg.cpu().numpy()
         r = P.reference_gradient(v, integ, reparam)
         e_plain, e_rest, windows = P.image_rel_l2_but_flips(img[0].cpu().numpy(), r['img64'], FWD_TOL, v['spp'])
@@ -240,6 +244,12 @@ def test_gradient_pass_ragged(dsdf, name, integ, reparam):
             if not named:
                 fails.append((msg, why))
     assert not fails, fails
+    # the sweep's hand-off to k_tail_trace_diff (whose finished samples splat their value on their own) is part of what these cases
+    # cover: once every case has run, at least one has handed rays off
+    SWEEP_TAILS[(name, integ, reparam)] = tails
+    P.record('tail_rays_sweep_ragged', case=name, integ=integ, reparam=reparam, tail_rays=tails)
+    if len(SWEEP_TAILS) == 3 * len(NAMES):
+        assert max(SWEEP_TAILS.values()) > 0, SWEEP_TAILS
 
 
 # a view whose plain gradient error exceeds the gate may set aside cubes only up to this share of the grid's voxels (a 7^3 cube is
