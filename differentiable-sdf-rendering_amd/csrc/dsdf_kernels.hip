@@ -29,6 +29,7 @@
 //                              scatter into dL/dsdf                                                           [dsdf_wave.h]
 //   k_forward_tangent          forward mode: the same queue, tangent film
 //   k_redist_*, k_mesh_raycast redistancing, mesh ray caster                              [dsdf_redistance.h, dsdf_mesh.h]
+//   k_mesh_morton, k_bvh_*, k_mesh_bvh_raycast, k_mesh_render<NCH>   mesh BVH: build, stackless traversal, primal render of a mesh   [dsdf_bvh.h]
 //
 // wave = 64 lanes; one lane = one film sample, consecutive lanes = consecutive
 // samples of the same pixel (reference lane order, reparam.py:140-155), so for
@@ -1991,4 +1992,5 @@ int dsdf_kernel_timing_read(float *ms) {
 }  // extern "C"
 
 #include "dsdf_redistance.h"
+#include "dsdf_bvh.h"
 #include "dsdf_mesh.h"

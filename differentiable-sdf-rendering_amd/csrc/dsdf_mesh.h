@@ -1,8 +1,8 @@
 // dsdf_mesh.h -- closest-hit ray / triangle-soup casting (included by dsdf_kernels.hip): the one native operation
 // `mesh_to_sdf.create_sdf` (python/mesh_to_sdf.py:9-57) takes from Mitsuba (`scene.ray_intersect` on an obj / ply shape).
 // Asset preparation, not the per-iteration hot path: brute force, N-body style -- a block stages DSDF_MESH_TILE triangles in
-// LDS (36 B each, read as broadcasts) and every thread tests its ray against them (Moeller-Trumbore, 1 ulp reciprocal-free
-// form); rays x triangles tests at ~10^12 / s: 128^3 voxel-centre rays x 20 k triangles in a fraction of a second, the
+// LDS (36 B each, read as broadcasts) and every thread tests its ray against them (tri_intersect, dsdf_bvh.h: the one statement of
+// the triangle test, shared with the BVH traversal that serves large meshes); rays x triangles tests at ~10^12 / s: 128^3 voxel-centre rays x 20 k triangles in a fraction of a second, the
 // 256-direction refinement of a 256^3 grid against 100 k triangles in tens of seconds.
 #pragma once
 
@@ -26,21 +26,10 @@ __global__ __launch_bounds__(256) void k_mesh_raycast(const float *__restrict__ 
         for (int e = threadIdx.x; e < cnt * 9; e += blockDim.x) tile[e] = tri[(size_t)t0 * 9 + e];
         __syncthreads();
         for (int k = 0; k < cnt; ++k) {
-            const float *p = tile + k * 9;
-            const V3 p0 = mk(p[0], p[1], p[2]), e1 = mk(p[3] - p[0], p[4] - p[1], p[5] - p[2]), e2 = mk(p[6] - p[0], p[7] - p[1], p[8] - p[2]);
-            // Moeller-Trumbore: o + t d = p0 + u e1 + v e2
-            const V3 pv = mk(d.y * e2.z - d.z * e2.y, d.z * e2.x - d.x * e2.z, d.x * e2.y - d.y * e2.x);
-            const float det = dot(e1, pv);
-            if (det == 0.f) continue;
-            const float inv = 1.f / det;
-            const V3 tv = o - p0;
-            const float u = dot(tv, pv) * inv;
-            const V3 qv = mk(tv.y * e1.z - tv.z * e1.y, tv.z * e1.x - tv.x * e1.z, tv.x * e1.y - tv.y * e1.x);
-            const float v = dot(d, qv) * inv;
-            const float t = dot(e2, qv) * inv;
-            if (u >= 0.f && v >= 0.f && u + v <= 1.f && t > t_min && t < best) {
-                best = t;
-                back = det < 0.f ? 1 : 0;          // det = e1 . (d x e2) = -d . (e1 x e2): negative when the normal points along the ray
+            TriHit h;
+            if (tri_intersect(tile + k * 9, o, d, h) && h.t > t_min && h.t < best) {
+                best = h.t;
+                back = h.det < 0.f ? 1 : 0;        // det = e1 . (d x e2) = -d . (e1 x e2): negative when the normal points along the ray
             }
         }
     }

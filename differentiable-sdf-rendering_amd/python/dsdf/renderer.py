@@ -820,6 +820,72 @@ def mesh_raycast(triangles, rays_o, rays_d, t_min=0.0):
     return t, back
 
 
+class MeshBvh:
+    """A bounding-volume hierarchy over a triangle soup in one device buffer (include/dsdf.h: the layout is ABI): Morton codes of
+    the centroids (dsdf_mesh_morton), a stable torch sort -- plumbing -- and the build (dsdf_mesh_bvh_build).  `triangles`
+    (T,3,3) and the optional per-corner `normals` (T,3,3) are device tensors; with normals the mesh renders smooth-shaded."""
+
+    def __init__(self, triangles, normals=None):
+        lib = _lib.load()
+        tri = _require_dev(triangles.reshape(-1, 9), 'triangles')
+        T = int(tri.shape[0])
+        if T < 1:
+            raise _lib.DsdfError("MeshBvh needs at least one triangle")
+        nrm = None
+        if normals is not None:
+            nrm = _require_dev(normals.reshape(-1, 9), 'normals')
+            if nrm.shape[0] != T:
+                raise _lib.DsdfError(f"normals must be (T,3,3) like triangles, got {tuple(normals.shape)}")
+        self.device, self.n_triangles, self.has_normals = tri.device, T, nrm is not None
+        self.buffer = torch.empty(int(lib.dsdf_mesh_bvh_size(T, int(nrm is not None))), dtype=torch.float32, device=tri.device)
+        codes = torch.empty(T, dtype=torch.int32, device=tri.device)
+        with torch.cuda.device(tri.device):
+            _lib.check(lib.dsdf_mesh_morton(_ptr(tri), T, _ptr(codes), _stream()))
+            self.order = torch.sort(codes, stable=True).indices.to(torch.int32)
+            _lib.check(lib.dsdf_mesh_bvh_build(_ptr(tri), _ptr(nrm), _ptr(self.order), T, _ptr(self.buffer), _stream()))
+
+    def raycast(self, rays_o, rays_d, t_min=0.0, return_prim=False):
+        """mesh_raycast through the hierarchy: (t, backface[, prim]) -- bit for bit the brute-force result; prim is the index of
+        the hit triangle in `triangles`, -1 on a miss."""
+        lib = _lib.load()
+        rays_o = _require_dev(rays_o, 'rays_o'); rays_d = _require_dev(rays_d, 'rays_d')
+        n = rays_o.shape[0]
+        t = torch.empty(n, dtype=torch.float32, device=rays_o.device)
+        back = torch.empty(n, dtype=torch.int32, device=rays_o.device)
+        prim = torch.empty(n, dtype=torch.int32, device=rays_o.device) if return_prim else None
+        with torch.cuda.device(rays_o.device):
+            _lib.check(lib.dsdf_mesh_bvh_raycast(_ptr(self.buffer), _ptr(rays_o), _ptr(rays_d), n, C.c_float(t_min), _ptr(t), _ptr(back),
+                                                 _ptr(prim), _stream()))
+        return (t, back, prim) if return_prim else (t, back)
+
+
+def mesh_render(bvh, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SILHOUETTE, shading=None, emitter_samples=None,
+                params=None):
+    """Primal render of a triangle mesh (dsdf_mesh_render_forward): render_forward with the intersection routine swapped -- the
+    reference images of a mesh scene (python/optimize.py:11-40) -> (n_views, H, W, 3).  `shading` (dsdf.Shading, diffuse, no
+    use_mis) and `emitter_samples` belong to sdf_direct_reparam; `params` carries the clip planes and the light direction."""
+    lib = _lib.load()
+    sensors, cams, W, H = _views(sensors)
+    nv, spp = len(sensors), int(spp)
+    n_lanes = (W + 4) * (H + 4) * spp
+    offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
+    integ = INTEGRATORS[integrator]
+    prm = params if params is not None else _lib.default_params()
+    sh = keep = None
+    if integ == DSDF_DIRECT:
+        if shading is None:
+            raise _lib.DsdfError("sdf_direct_reparam needs shading=dsdf.Shading(albedo, ...)")
+        st, keep = shading.to_struct(nv, n_lanes, emitter_samples)
+        sh = C.byref(st)
+    dev = bvh.device
+    img = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.dsdf_mesh_render_workspace_size(W, H, min(nv, MAX_VIEWS_PER_LAUNCH)), lib.dsdf_mesh_render_workspace_size(W, H, 1))
+    with torch.cuda.device(dev):
+        _lib.check(lib.dsdf_mesh_render_forward(_ptr(bvh.buffer), C.byref(prm), cams, nv, W, H, spp, _ptr(offsets), cseeds, integ, sh,
+                                                _ptr(img), _ptr(ws), ws.numel(), _stream()))
+    return img
+
+
 def kernel_timing_arm():
     """Measurement hook (include/dsdf.h): the next render call brackets its render kernel with HIP events."""
     _lib.check(_lib.load().dsdf_kernel_timing_arm())

@@ -14,6 +14,7 @@ import dsdf
 import redistancing
 
 ANGULAR_RES = 16            # mesh_to_sdf.py:40: 16 x 16 stratified directions per near-surface voxel
+BVH_MIN_TRIANGLES = 4096    # accel=None: meshes above this go through dsdf.MeshBvh, smaller ones through the brute-force kernel
 
 
 def load_obj(fn):
@@ -116,12 +117,35 @@ def load_ply(fn):
     return verts, np.asarray(faces, np.int64).reshape(-1, 3)
 
 
-def load_mesh(mesh_fn):
-    """(T, 3, 3) float32 triangle corners; the plugin is chosen the way the reference does (mesh_to_sdf.py:12)."""
+def load_mesh_indexed(mesh_fn):
+    """(V, 3) float32 vertices and (T, 3) faces; the plugin is chosen the way the reference does (mesh_to_sdf.py:12)."""
     v, f = load_obj(mesh_fn) if mesh_fn.endswith('.obj') else load_ply(mesh_fn)
     if len(f) == 0:
         raise ValueError(f'{mesh_fn}: no faces')
+    return v, f
+
+
+def load_mesh(mesh_fn):
+    """(T, 3, 3) float32 triangle corners."""
+    v, f = load_mesh_indexed(mesh_fn)
     return v[f]
+
+
+def vertex_normals(v, f, smooth=True):
+    """(T, 3, 3) float32 normals at the corners of every triangle.  smooth: angle-weighted vertex normals (what Mitsuba computes
+    for a mesh file that carries none); otherwise every corner takes its triangle's face normal."""
+    p = np.asarray(v, np.float64)[f]
+    fn = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    fn /= np.maximum(np.linalg.norm(fn, axis=1, keepdims=True), 1e-300)
+    if not smooth:
+        return np.repeat(fn[:, None, :], 3, 1).astype(np.float32)
+    vn = np.zeros((len(v), 3))
+    for k in range(3):
+        a, b = p[:, (k + 1) % 3] - p[:, k], p[:, (k + 2) % 3] - p[:, k]
+        cosang = (a * b).sum(1) / np.maximum(np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1), 1e-300)
+        np.add.at(vn, f[:, k], fn * np.arccos(np.clip(cosang, -1.0, 1.0))[:, None])
+    vn /= np.maximum(np.linalg.norm(vn, axis=1, keepdims=True), 1e-300)
+    return vn[f].astype(np.float32)
 
 
 def voxel_centres(res, device):
@@ -142,7 +166,17 @@ def sphere_directions(device, angular_res=ANGULAR_RES):
     return torch.stack([rad * torch.cos(phi), rad * torch.sin(phi), zc], -1).contiguous()
 
 
-def occupancy(triangles, res):
+def _caster(triangles, accel=None):
+    """(rays_o, rays_d) -> (t, backface) for this mesh.  accel: 'brute' = dsdf.mesh_raycast, every ray against every triangle;
+    'bvh' = dsdf.MeshBvh; None = the BVH above BVH_MIN_TRIANGLES triangles.  Both give the same bits."""
+    if accel not in (None, 'bvh', 'brute'):
+        raise ValueError(f"accel must be None, 'bvh' or 'brute', got {accel!r}")
+    if accel == 'bvh' or (accel is None and triangles.shape[0] > BVH_MIN_TRIANGLES):
+        return dsdf.MeshBvh(triangles).raycast
+    return lambda o, d: dsdf.mesh_raycast(triangles, o, d)
+
+
+def occupancy(triangles, res, cast=None):
     """0.5 - inside, inside = the +y ray from the voxel centre leaves the solid through its first hit (mesh_to_sdf.py:23-27).
     The reference casts that one ray with Embree / OptiX, whose intersectors are edge-consistent; dsdf_mesh_raycast tests every
     triangle on its own (Moeller-Trumbore), so a ray through a shared edge or vertex -- voxel centres sit on the symmetry planes
@@ -150,10 +184,11 @@ def occupancy(triangles, res):
     through a back face in every direction); where the two disagree a third, generic direction decides."""
     dev = triangles.device
     o = voxel_centres(res, dev)
+    cast = cast or _caster(triangles, 'brute')
 
     def inside_along(direction):
         d = torch.tensor(direction, dtype=torch.float32, device=dev).expand_as(o).contiguous()
-        t, back = dsdf.mesh_raycast(triangles, o, d)
+        t, back = cast(o, d)
         return torch.isfinite(t) & (back != 0)
     up, down = inside_along((0.0, 1.0, 0.0)), inside_along((0.0, -1.0, 0.0))
     inside = up
@@ -164,9 +199,10 @@ def occupancy(triangles, res):
     return (0.5 - inside.float()).reshape(res, res, res), o
 
 
-def refine(triangles, grid, origins, res, chunk=1 << 16):
+def refine(triangles, grid, origins, res, chunk=1 << 16, cast=None):
     """Near-surface voxels (|phi| < 1/res) take the minimum hit distance over the sphere directions, signed by the
     redistanced occupancy (mesh_to_sdf.py:32-55).  No hit in any direction keeps the reference's 100.0."""
+    cast = cast or _caster(triangles, 'brute')
     flat = grid.reshape(-1).clone()
     near = torch.nonzero(flat.abs() < 1.0 / res).reshape(-1)
     dirs = sphere_directions(flat.device)
@@ -175,20 +211,21 @@ def refine(triangles, grid, origins, res, chunk=1 << 16):
         idx = near[s:s + chunk]
         o = origins[idx].repeat_interleave(nd, 0)
         d = dirs.repeat(idx.numel(), 1)
-        t, _ = dsdf.mesh_raycast(triangles, o, d)
+        t, _ = cast(o, d)
         md = torch.clamp(t.reshape(-1, nd).min(1).values, max=100.0)
         flat[idx] = torch.where(flat[idx] < 0, -md, md)          # dr.sign(0) = +1
     return flat.reshape(res, res, res)
 
 
-def create_sdf(mesh_fn, resolution, refine_surface=True, device='cuda'):
+def create_sdf(mesh_fn, resolution, refine_surface=True, device='cuda', accel=None):
     """Convert a watertight mesh to an SDF using ray casting and redistancing.  `mesh_fn`: path of an obj / ply file, or a
-    (T, 3, 3) tensor / array of triangle corners."""
+    (T, 3, 3) tensor / array of triangle corners.  accel: how the rays are cast (_caster); the result does not depend on it."""
     tri = load_mesh(mesh_fn) if isinstance(mesh_fn, str) else mesh_fn
     tri = torch.as_tensor(np.asarray(tri) if not torch.is_tensor(tri) else tri, dtype=torch.float32).to(device).reshape(-1, 3, 3).contiguous()
     res = int(resolution)
-    values, origins = occupancy(tri, res)
+    cast = _caster(tri, accel)
+    values, origins = occupancy(tri, res, cast)
     grid = redistancing.redistance(values)
     if refine_surface:
-        grid = redistancing.redistance(refine(tri, grid, origins, res))
+        grid = redistancing.redistance(refine(tri, grid, origins, res, cast=cast))
     return grid

@@ -5,7 +5,8 @@ that is not part of the repository, README.md:59-68) and renders the reference i
 mesh.  Here a scene is just a target SDF volume: `scenes/<scene>/<scene>.vol` if present, a
 watertight mesh `scenes/<scene>/<scene>.obj` / `.ply` inside [-0.5, 0.5]^3 converted with
 `mesh_to_sdf.create_sdf` (python/mesh_to_sdf.py:9-57), else a procedural shape (`sphere`, `torus`, `blobs`, or -- for any other name such as `dragon` -- a
-union of primitives seeded by the scene name), rendered with the same integrator."""
+union of primitives seeded by the scene name), rendered with the same integrator.  `load_target_mesh` returns the mesh of a
+scene that has one, for reference images rendered from the mesh itself (`optimize.py --meshrefs`)."""
 import hashlib
 import os
 
@@ -58,6 +59,21 @@ def load_target_sdf(scene_name, res=128, device='cuda'):
     seed = 0 if scene_name == 'blobs' else int(hashlib.sha1(scene_name.encode()).hexdigest()[:8], 16)
     print(f"[scenes] no assets for '{scene_name}' under {SCENE_DIR}; using a procedural stand-in (seed {seed})")
     return _blobs(res, seed, device)
+
+
+def load_target_mesh(scene_name, smooth=True, device='cuda'):
+    """The scene's mesh itself, for reference images rendered from it (dsdf.mesh_render): (triangles, normals), both (T,3,3) float32
+    on `device`, shifted by +0.5 from the readers' [-0.5, 0.5]^3 into the SDF's unit cube (the sensors look at (0.5, 0.5, 0.5)) -- or
+    None when the scene has no mesh.  smooth: angle-weighted vertex normals (Mitsuba's for a file without normals), else face normals."""
+    for ext in ('.obj', '.ply'):
+        mesh = os.path.join(SCENE_DIR, scene_name, scene_name + ext)
+        if os.path.isfile(mesh):
+            import mesh_to_sdf
+            v, f = mesh_to_sdf.load_mesh_indexed(mesh)
+            tri = torch.as_tensor(v[f] + np.float32(0.5), dtype=torch.float32, device=device).contiguous()
+            nrm = torch.as_tensor(mesh_to_sdf.vertex_normals(v, f, smooth), dtype=torch.float32, device=device).contiguous()
+            return tri, nrm
+    return None
 
 
 def load_target_albedo(scene_name, res=32, device='cuda'):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DSDF_VERSION 308   /* 308: dsdf_cell_table_size, row-block copy in the grid buffer (dsdf_padded_size grew); 307: dsdf_tail_stats_arm; 300: stats rows of DSDF_STAT_SLOTS (16) counters; tail hand-off on library-owned helper streams; 304: DSDF_NO_HIT_PROOF, the grid buffer carries the bounds of the hit proof (dsdf_padded_size); 305: dsdf_params grows by normalize_warp_field, max_reparam_depth; 306: dsdf_render_aovs, dsdf_aov_workspace_size, dsdf_sampler_2d, dsdf_set_grid_transform / dsdf_has_grid_transform, dsdf_shading.bsdf_lobe_samples */
+#define DSDF_VERSION 308   /* 308 (additive, same number: no existing entry point or struct changed): dsdf_mesh_bvh_size, dsdf_mesh_morton, dsdf_mesh_bvh_build, dsdf_mesh_bvh_raycast, dsdf_mesh_render_workspace_size, dsdf_mesh_render_forward; 308: dsdf_cell_table_size, row-block copy in the grid buffer (dsdf_padded_size grew); 307: dsdf_tail_stats_arm; 300: stats rows of DSDF_STAT_SLOTS (16) counters; tail hand-off on library-owned helper streams; 304: DSDF_NO_HIT_PROOF, the grid buffer carries the bounds of the hit proof (dsdf_padded_size); 305: dsdf_params grows by normalize_warp_field, max_reparam_depth; 306: dsdf_render_aovs, dsdf_aov_workspace_size, dsdf_sampler_2d, dsdf_set_grid_transform / dsdf_has_grid_transform, dsdf_shading.bsdf_lobe_samples */
 #define DSDF_STAT_SLOTS 16
 
 enum dsdf_status {
@@ -394,6 +394,46 @@ int dsdf_redistance_counters(const void *workspace, int rx, int ry, int rz, int3
  * mesh_to_sdf.py:26: the ray leaves the solid, its origin is inside.  Brute force (asset preparation, not the hot path). */
 int dsdf_mesh_raycast(const float *triangles, int n_triangles, const float *rays_o, const float *rays_d, int64_t n,
                       float t_min, float *t_out, int32_t *backface_out, void *stream);
+
+/* ---- mesh BVH: ray casts against large meshes, and reference images rendered from the mesh itself (python/optimize.py:11-40) ----
+ * An implicit COMPLETE binary tree in ONE caller-owned device buffer of dsdf_mesh_bvh_size() floats (64-byte aligned).  T triangles,
+ * 4 per leaf, L = the smallest power of two >= ceil(T / 4) leaves, L - 1 inner nodes in heap order (children of node i: 2 i + 1 and
+ * 2 i + 2; leaf j is heap node L - 1 + j).  Layout, in floats (ints are stored by bit pattern):
+ *   [0, 16)        header: int T, int L, int has_normals, float margin, float lo[3], float hi[3] (the mesh AABB), 6 x 0
+ *   [16, 16 L)     inner node i at 16 + 16 i: box of child 0 (lo.xyz, hi.xyz), box of child 1, 4 x 0: one 64-byte fetch
+ *   [16 L, 64 L)   triangle slot s at 16 L + 12 s -- leaf j owns slots 4 j .. 4 j + 3, filled from the left in the order of the caller's
+ *                  permutation: p0, p1, p2, int original index (-1: empty slot), 2 x 0
+ *   [64 L, 100 L)  with normals only: slot s at 64 L + 9 s: the vertex normals n0, n1, n2 of the triangle in that slot
+ * Surplus leaves are empty and have the inverted box lo = +inf, hi = -inf, which no ray enters.  Leaf boxes are grown by
+ * `margin` = 2^-13 x the largest extent of the mesh AABB, and triangles with (nearly) collinear corners get an infinite box, so that
+ * the traversal never culls a triangle the loop over all triangles would accept: dsdf_mesh_bvh_raycast returns bit for bit what
+ * dsdf_mesh_raycast returns (origins within a few extents of the mesh).  Nothing here allocates or synchronises. */
+size_t dsdf_mesh_bvh_size(int n_triangles, int has_normals);
+
+/* The 30-bit Morton code of every triangle's centroid inside the mesh AABB: codes_out n_triangles int32.  The caller sorts
+ * (`torch.sort(codes, stable=True)`: sorting is plumbing, the library has no device sort) and passes the permutation to the build. */
+int dsdf_mesh_morton(const float *triangles, int n_triangles, int32_t *codes_out, void *stream);
+
+/* Builds the buffer: gathers the triangles (n x 9) [and their vertex normals, n x 9, or NULL] through `order` (n int32: slot s takes
+ * triangle order[s]; NULL = the given order), writes the leaf boxes and fits the levels bottom-up, one launch per level. */
+int dsdf_mesh_bvh_build(const float *triangles, const float *normals, const int32_t *order, int n_triangles, float *bvh, void *stream);
+
+/* dsdf_mesh_raycast through the BVH: same t_out / backface_out, bit for bit; prim_out n (optional, int32): the ORIGINAL index of the hit
+ * triangle, -1 on a miss.  On equal t the lower original index wins, as in the loop over all triangles. */
+int dsdf_mesh_bvh_raycast(const float *bvh, const float *rays_o, const float *rays_d, int64_t n, float t_min, float *t_out,
+                          int32_t *backface_out, int32_t *prim_out, void *stream);
+
+/* Primal render of the mesh: dsdf_render_forward with the intersection routine swapped -- same lane order, sampler rules (offsets /
+ * seeds), camera ray, film block, re-projection and develop; no reparameterisation (det = 1).  Per sample: DSDF_SILHOUETTE [hit];
+ * DSDF_SIMPLE_SHADING max(n . prm->light_dir, 0); DSDF_DIRECT the emitter-sampling statement of sdf_direct_reparam.py:29-75 with the
+ * `diffuse` BSDF over shading->albedo (evaluated at the hit point) and an any-hit shadow query (shading->bsdf and ->use_mis must be 0;
+ * ->emitter_samples, ->env_radiance, ->hide_emitters as in dsdf_render_forward).  n: the normalised interpolation of the stored vertex
+ * normals, or without them the geometric normal (p1 - p0) x (p2 - p0).  Any spp >= 1.  workspace: dsdf_mesh_render_workspace_size()
+ * bytes (film blocks of one launch; one view's worth is always enough). */
+size_t dsdf_mesh_render_workspace_size(int width, int height, int n_views);
+int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsdf_camera *cams, int n_views, int width, int height, int spp,
+                             const float *offsets, const uint32_t *seeds, int integrator, const dsdf_shading *shading, float *image_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
