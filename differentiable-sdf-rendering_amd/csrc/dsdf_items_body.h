@@ -43,7 +43,7 @@
         const int py = (int)(pix / (uint32_t)A.Wb), px = (int)(pix - (uint32_t)py * (uint32_t)A.Wb);
         // empty-space proof of this pixel: the result of tracing is known -- a miss with no warp -- so the loop is skipped
         const unsigned proof = skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)skip[e]) : 0u;
-        const bool skip_trace = (proof & (DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY)) != 0;
+        const bool skip_trace = px_skip_trace<DIFF>(proof);
         // hit proof of this pixel (silhouette primal): every sample hits, and only the hit flag is consumed
         const bool known_hit = !DIFF && !DIRECT && (proof & DSDF_PX_HIT) && A.integrator == DSDF_SILHOUETTE;
         const uint32_t unit = pix * chunks + item % chunks;

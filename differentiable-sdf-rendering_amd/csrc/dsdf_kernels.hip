@@ -442,7 +442,7 @@ __global__ __launch_bounds__(64) void k_direct_items(GridView G, dsdf_params P, 
             const ViewArgs &A = VB.v[view];
             const int py = (int)(pix / (uint32_t)A.Wb), px = (int)(pix - (uint32_t)py * (uint32_t)A.Wb);
             const unsigned proof = skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)skip[e]) : 0u;
-            const bool skip_trace = (proof & (DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY)) != 0;
+            const bool skip_trace = px_skip_trace<DIFF>(proof);
             float acc[NCH][2];
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) { acc[ch][0] = 0.f; acc[ch][1] = 0.f; }
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(DSDF_BLOCK) void k_render_pass(GridView G, dsdf_par
         lane_pixel(A, lane, px, py);
         if (skip) {
             const unsigned f = skip[(size_t)blockIdx.y * A.Wb * A.Hb + (size_t)py * A.Wb + px];
-            skip_trace = (f & (DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY)) != 0;
+            skip_trace = px_skip_trace<DIFF>(f);
             far = (f & (DIFF ? DSDF_PX_FAR_G : DSDF_PX_FAR)) != 0 && !(DIRECT && !S.hide_emitters && !M.env_fill);   // (a visible environment is not zero: k_film_env)
             // (hit proof: the samples of a deep pixel only reach film pixels that develop to 1 anyway; M.deep_mask = DSDF_PX_DEEP or 0)
             if (!DIFF && !DIRECT && (f & M.deep_mask) && A.integrator == DSDF_SILHOUETTE) far = true;
@@ -1209,23 +1209,15 @@ size_t dsdf_padded_size(int rx, int ry, int rz) {
 
 int dsdf_pad_grid(const float *data, int rx, int ry, int rz, float *padded, void *stream) {
     if (!data || !padded || rx < 1 || ry < 1 || rz < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_pad_grid: bad argument");
+#if DSDF_TLAYOUT
+    if ((uint64_t)32 * (ry + 2 * DSDF_APRON) * (rz + 2 * DSDF_APRON) >= (1u << 24) || tlayout_floats(rx, ry, rz) * 4 >= ((uint64_t)1 << 32))
+        return fail(DSDF_ERR_INVALID_ARG, "dsdf_pad_grid: grid too large for the row-block copy (24-bit stride, 32-bit offsets: about 717^3)");
+#endif
     size_t n = padded_floats(rx, ry, rz);
     int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
     hipLaunchKernelGGL(k_pad_grid, dim3(grid), dim3(256), 0, (hipStream_t)stream, data, rx, ry, rz, padded);
     int rc = check_launch("k_pad_grid");
     if (rc) return rc;
-#if DSDF_TLAYOUT
-    {
-        if ((uint64_t)32 * (ry + 2 * DSDF_APRON) * (rz + 2 * DSDF_APRON) >= (1u << 24) || tlayout_floats(rx, ry, rz) * 4 >= ((uint64_t)1 << 32))
-            return fail(DSDF_ERR_INVALID_ARG, "dsdf_pad_grid: grid too large for the row-block copy (24-bit stride, 32-bit offsets: about 717^3)");
-        const int sx = rx + 2 * DSDF_APRON, sy = ry + 2 * DSDF_APRON, sz = rz + 2 * DSDF_APRON, nxc = (int)tlayout_chunks(rx);
-        const size_t nt = (size_t)nxc * sz * sy * 2;
-        const int tg = (int)((nt + 255) / 256 < 16384 ? (nt + 255) / 256 : 16384);
-        hipLaunchKernelGGL(k_tlayout, dim3(tg), dim3(256), 0, (hipStream_t)stream, (const float *)padded, sx, sy, sz, nxc,
-                           padded + tlayout_offset(rx, ry, rz));
-        if ((rc = check_launch("k_tlayout"))) return rc;
-    }
-#endif
     // conservative min-grids for the empty-space proof, max-grid for the hit proof
     float *c0 = padded + n;
     for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) {
@@ -1247,15 +1239,37 @@ int dsdf_pad_grid(const float *data, int rx, int ry, int rz, float *padded, void
                            1 << DSDF_HIT_SHIFT);
         hipLaunchKernelGGL(k_coarse_dilate<true>, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, c0, c1, cx, cy, cz, DSDF_HIT_RADIUS);
     }
-    {   // fine window maxima: x pass (data -> F), y pass (F -> scratch), z pass (scratch -> F)
-        float *F = fine_buffer(padded, rx, ry, rz), *T = F + (size_t)rx * ry * rz;
+    {   // fine window maxima F and minima S, three separable passes each (x, y, z)
+        float *F = fine_buffer(padded, rx, ry, rz), *S = F + (size_t)rx * ry * rz;
         const size_t total = (size_t)rx * ry * rz;
         const dim3 g((unsigned)((total + 255) / 256)), b(256);
-        hipLaunchKernelGGL(k_window_max, g, b, 0, (hipStream_t)stream, data, F, total, rx, (size_t)1, DSDF_FINE_LO, DSDF_FINE_HI);
-        hipLaunchKernelGGL(k_window_max, g, b, 0, (hipStream_t)stream, (const float *)F, T, total, ry, (size_t)rx, DSDF_FINE_LO, DSDF_FINE_HI);
-        hipLaunchKernelGGL(k_window_max, g, b, 0, (hipStream_t)stream, (const float *)T, F, total, rz, (size_t)rx * ry, DSDF_FINE_LO, DSDF_FINE_HI);
+        const hipStream_t st = (hipStream_t)stream;
+#if DSDF_TLAYOUT
+        // (the passes ping-pong through the region of the row-block copy, larger than the grid, which k_tlayout fills AFTER them:
+        // so the second full-resolution buffer, once their scratch, is free to hold the minima)
+        float *T = padded + tlayout_offset(rx, ry, rz);
+        hipLaunchKernelGGL(k_window<false>, g, b, 0, st, data, S, total, rx, (size_t)1, DSDF_FINE_LO, DSDF_FINE_HI);
+        hipLaunchKernelGGL(k_window<false>, g, b, 0, st, (const float *)S, T, total, ry, (size_t)rx, DSDF_FINE_LO, DSDF_FINE_HI);
+        hipLaunchKernelGGL(k_window<false>, g, b, 0, st, (const float *)T, S, total, rz, (size_t)rx * ry, DSDF_FINE_LO, DSDF_FINE_HI);
+#else
+        float *T = S;
+#endif
+        hipLaunchKernelGGL(k_window<true>, g, b, 0, st, data, F, total, rx, (size_t)1, DSDF_FINE_LO, DSDF_FINE_HI);
+        hipLaunchKernelGGL(k_window<true>, g, b, 0, st, (const float *)F, T, total, ry, (size_t)rx, DSDF_FINE_LO, DSDF_FINE_HI);
+        hipLaunchKernelGGL(k_window<true>, g, b, 0, st, (const float *)T, F, total, rz, (size_t)rx * ry, DSDF_FINE_LO, DSDF_FINE_HI);
     }
-    return check_launch("k_coarse_reduce/dilate");
+    if ((rc = check_launch("k_coarse_reduce/dilate/window"))) return rc;
+#if DSDF_TLAYOUT
+    {   // the row-block copy, behind the window passes above, which use its region as their temporary
+        const int sx = rx + 2 * DSDF_APRON, sy = ry + 2 * DSDF_APRON, sz = rz + 2 * DSDF_APRON, nxc = (int)tlayout_chunks(rx);
+        const size_t nt = (size_t)nxc * sz * sy * 2;
+        const int tg = (int)((nt + 255) / 256 < 16384 ? (nt + 255) / 256 : 16384);
+        hipLaunchKernelGGL(k_tlayout, dim3(tg), dim3(256), 0, (hipStream_t)stream, (const float *)padded, sx, sy, sz, nxc,
+                           padded + tlayout_offset(rx, ry, rz));
+        if ((rc = check_launch("k_tlayout"))) return rc;
+    }
+#endif
+    return DSDF_OK;
 }
 
 int dsdf_eval_cubic(const float *padded, int rx, int ry, int rz, const dsdf_params *prm, const float *points,
@@ -1422,6 +1436,7 @@ struct SkipShare {
     const float *padded = nullptr;
     int rx = 0, ry = 0, rz = 0, W = 0, H = 0, nv = 0;
     int hit_proof = 0;     // the flags carry DSDF_PX_HIT (silhouette integrator, hit proof not disabled)
+    int fine_empty = 0;    // the flags carry the second stage of the empty-space proof (bit 7, more of bit 1)
     dsdf_params prm;
     dsdf_camera cams[DSDF_MAX_BATCH];
 };
@@ -1430,6 +1445,7 @@ static thread_local SkipShare t_share;
 static bool skip_share_matches(const SkipShare &h, const PassCtx &c, const dsdf_camera *cams, int nv) {
     return h.valid && h.padded == c.padded && h.rx == c.rx && h.ry == c.ry && h.rz == c.rz && h.W == c.W && h.H == c.H && h.nv == nv &&
            h.hit_proof <= (int)(c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF)) &&      // (flags WITHOUT hit bits serve any call)
+           h.fine_empty <= (int)!(c.flags & DSDF_NO_FINE_EMPTY) &&                                         // (and so do flags without the fine stage)
            memcmp(&h.prm, c.prm, sizeof(dsdf_params)) == 0 && memcmp(h.cams, cams, (size_t)nv * sizeof(dsdf_camera)) == 0;
 }
 
@@ -1455,25 +1471,33 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     unsigned char *dst = (can_share && !sh.valid) ? sh.buf : ws.skip;       // (a second, different batch keeps its own flags)
     const bool want_hit = c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF) && c.spp >= HIT_PROOF_MIN_SPP;
     const float hstep = want_hit ? hit_step(cams, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
-    const float fstep = want_hit ? hit_step_fine(cams, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
+    // the second stage on the full-resolution bounds: the fine hit proof where the hit proof is wanted, the fine empty-space proof
+    // for every integrator (DSDF_NO_FINE_EMPTY, or a build without the window minima: off)
+    const float fstep = hit_step_fine(cams, nv, c.W, c.rx, c.ry, c.rz);
+    const BoundGrid none = {nullptr, 0, 0, 0, 0, 0.f};
+    const BoundGrid fmin = (c.flags & DSDF_NO_FINE_EMPTY) ? none : fine_min_bounds(c.padded, c.rx, c.ry, c.rz);
+    const bool fine = fstep > 0.f && (want_hit || fmin.b);
+    // (a gradient pass reads these flags -- this call, or a later one of the bracket: the pixels with bit 0 but not bit 1 are listed too)
+    const int list_g = (fmin.b && (c.diff || dst == sh.buf)) ? 1 : 0;
     // the pixels neither proof settles are listed in the (not yet built) work-list area of this workspace for the second
-    // stage of the hit proof: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
-    uint32_t *und = fstep > 0.f ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
+    // stage: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
+    uint32_t *und = fine ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
     if (und && hipMemsetAsync(und, 0, sizeof(uint32_t), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(undecided list) failed");
     // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try)
     const float step0 = level > 0 ? skip_step(cams, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
     const dim3 pgrid((unsigned)((npix + 255) / 256), nv), blk(256);
     if ((rc = launch("k_pixel_skip", k_pixel_skip, pgrid, blk, st, device_view(c), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
-                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und)))
+                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und, list_g)))
         return rc;
     if (und && (rc = launch("k_pixel_hit_fine", k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), blk, st, device_view(c),
-                            fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, und, und + DSDF_UNDECIDED_HDR, fstep)))
+                            fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))
         return rc;
     if ((rc = launch("k_skip_dilate", k_skip_dilate, pgrid, blk, st, VB, dst))) return rc;
     if (dst == sh.buf) {
         if (hipEventRecord(sh.ready, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipEventRecord(shared skip flags) failed");
         sh.valid = true; sh.padded = c.padded; sh.rx = c.rx; sh.ry = c.ry; sh.rz = c.rz; sh.W = c.W; sh.H = c.H; sh.nv = nv;
         sh.hit_proof = (int)want_hit;
+        sh.fine_empty = (int)(fine && fmin.b);
         sh.prm = *c.prm;
         memcpy(sh.cams, cams, (size_t)nv * sizeof(dsdf_camera));
     }
@@ -1503,7 +1527,7 @@ static int prefill_film(const PassCtx &c, const Batch &b) {
     const dim3 grid((unsigned)((c.Wb * c.Hb + 255) / 256), b.nv), blk(256);
     if (b.deep_skip && (rc = launch("k_film_ones", k_film_ones, grid, blk, c.st, b.VB, b.skip, b.film, c.row0, c.row1, b.st64))) return rc;
     if (b.env_fill && (rc = launch("k_film_env", k_film_env, grid, blk, c.st, b.VB, b.skip, b.film, c.row0, c.row1,
-                                   DIFF ? DSDF_PX_EMPTY_G : DSDF_PX_EMPTY, b.S.env[0], b.S.env[1], b.S.env[2])))
+                                   DIFF ? DSDF_PX_EMPTY_G : (DSDF_PX_EMPTY | DSDF_PX_EMPTY_FINE), b.S.env[0], b.S.env[1], b.S.env[2])))
         return rc;
     return DSDF_OK;
 }

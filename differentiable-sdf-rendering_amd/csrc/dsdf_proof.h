@@ -7,6 +7,9 @@
 // all rays of the pixel at once:
 //   * empty-space proof  (bits 0 / 1): the lower bound stays above the hit threshold along the whole centre ray -> every
 //     sample misses (primal) and has a zero boundary weight (gradient pass);
+//     -- in two stages: on the dilated block minima (bits 0 / 1), then, for the pixels those leave, on full-resolution window
+//     minima (bits 7 / 1: hit_step_fine, k_pixel_hit_fine).  Bit 0 keeps meaning "proven by the BLOCK minima"; a reader that wants
+//     "the primal's samples all miss" asks px_primal_empty;
 //   * hit proof (bit 4, silhouette primal): see pixel_hit_proof -> every sample HITS.  The silhouette integrator consumes
 //     only the hit flag (sdf_silhouette_reparam.py:20-22), so such a pixel needs no march at all.
 // Both are proofs, not approximations: a flagged pixel gets exactly the flags tracing would produce
@@ -21,9 +24,16 @@
 #define DSDF_PX_HIT 16u        /* every sample of the pixel hits the surface */
 #define DSDF_PX_DEEP 32u       /* (k_skip_dilate) every pixel within +-4 carries bit 4: the samples reach only film pixels of value 1 */
 #define DSDF_PX_ONE 64u        /* (k_skip_dilate) every pixel within +-2 carries bit 4: this FILM pixel receives hits only */
-#define DSDF_PX_KEEP (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G | DSDF_PX_HIT)
+#define DSDF_PX_EMPTY_FINE 128u /* primal: every sample misses, proven by the second stage on the full-resolution window minima */
+#define DSDF_PX_KEEP (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G | DSDF_PX_HIT | DSDF_PX_EMPTY_FINE)
 
 namespace dsdf {
+
+// "Every sample of the pixel's PRIMAL misses": proven by either stage of the empty-space proof.
+DSDF_HD bool px_primal_empty(unsigned f) { return (f & (DSDF_PX_EMPTY | DSDF_PX_EMPTY_FINE)) != 0u; }
+// "The march of this pixel's samples is known without running it" for the pass that reads the flags: a miss (primal), a miss with a
+// zero boundary weight (gradient pass, bit 1 -- which either stage sets).
+template <bool DIFF> DSDF_HD bool px_skip_trace(unsigned f) { return DIFF ? (f & DSDF_PX_EMPTY_G) != 0u : px_primal_empty(f); }
 
 // Dilated block bounds behind the padded grid (dsdf_skip.h: device_view / hit_view): one coarse level.
 struct BoundGrid {
@@ -171,9 +181,9 @@ static int skip_level(const dsdf_camera *cams, int nv, int W, int rx, int ry, in
     return -1;
 }
 
-// The FINE bound of the hit proof (second stage, for the pixels the block maxima leave undecided): per B-spline cell c the
-// maximum over the taps [c - 2, c + 3]^3 -- every tap of every lookup within ONE voxel of a point of cell c -- at full
-// resolution (k_window_max, dsdf_skip.h).  A 6^3-voxel window instead of the 10^3 of the block maxima: shapes a few voxels
+// The FINE bounds (second stage of both proofs, for the pixels the block bounds leave undecided): per B-spline cell c the
+// maximum (hit proof) / minimum (empty-space proof) over the taps [c - 2, c + 3]^3 -- every tap of every lookup within ONE voxel
+// of a point of cell c -- at full resolution (k_window, dsdf_skip.h).  A 6^3-voxel window instead of the 10^3 of the block maxima: shapes a few voxels
 // thick and pixels close to the silhouette still prove.  Step of its march, or 0 when lateral deviation + half a step exceed
 // that one voxel (or the box argument of pixel_hit_proof fails).
 #define DSDF_FINE_LO (-2)

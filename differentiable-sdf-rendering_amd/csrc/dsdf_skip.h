@@ -38,16 +38,19 @@ __global__ void k_coarse_dilate(const float *__restrict__ c0, float *__restrict_
     c[i] = m;
 }
 
-// Sliding-window maximum along one axis (stride `st` elements, extent n): out[i] = max(in[clamp(i + lo .. i + hi)]).  Three passes
-// (x, y, z) build the fine bound of the hit proof (dsdf_proof.h: hit_step_fine) from sdf.data.
-__global__ void k_window_max(const float *__restrict__ in, float *__restrict__ out, size_t total, int n, size_t st, int lo, int hi) {
+// Sliding-window maximum / minimum along one axis (stride `st` elements, extent n): out[i] = max(in[clamp(i + lo .. i + hi)]).  Three
+// passes (x, y, z) build the fine bounds of the hit proof (maxima) and of the empty-space proof (minima) from sdf.data
+// (dsdf_proof.h: hit_step_fine).
+template <bool MAX>
+__global__ void k_window(const float *__restrict__ in, float *__restrict__ out, size_t total, int n, size_t st, int lo, int hi) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int a = (int)((i / st) % (size_t)n);
-    float m = -INFINITY;
+    float m = MAX ? -INFINITY : INFINITY;
     for (int o = lo; o <= hi; ++o) {
         const int b = min(max(a + o, 0), n - 1);
-        m = fmaxf(m, in[i + (size_t)(b - a) * st]);     // (b - a may be negative: size_t wrap-around adds up correctly)
+        const float v = in[i + (size_t)(b - a) * st];   // (b - a may be negative: size_t wrap-around adds up correctly)
+        m = MAX ? fmaxf(m, v) : fminf(m, v);
     }
     out[i] = m;
 }
@@ -55,12 +58,14 @@ __global__ void k_window_max(const float *__restrict__ in, float *__restrict__ o
 // flags[view][Hb*Wb]: DSDF_PX_EMPTY / _EMPTY_G / _HIT of every film-block pixel (dsdf_proof.h).  step == 0: no empty-space
 // proof, hstep == 0: no hit proof (margins not covered, or the integrator consumes more than the hit flag).
 // `undecided` (optional): [0] = counter (zeroed by the caller), entries from [DSDF_UNDECIDED_HDR]: view * Wb * Hb + pixel of every
-// pixel neither proof settled -- the work list of k_pixel_hit_fine.
+// pixel neither proof settled -- the work list of k_pixel_hit_fine -- and, with list_g (a gradient pass will read these flags and
+// the fine empty-space stage runs), of every pixel with bit 0 but not bit 1: the fine minima may still give it bit 1.
 #define DSDF_UNDECIDED_HDR 16
 // step0 > 0: a first, cheaper attempt at the empty-space proof on the next-coarser level Bmin0 (blocks twice as large, steps twice
 // as long): most pixels of a silhouette view pass far from the shape and are settled there.
 __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundGrid Bmax, dsdf_params P, ViewBatch VB,
-                             unsigned char *__restrict__ flags, float step0, float step, float hstep, uint32_t *__restrict__ undecided) {
+                             unsigned char *__restrict__ flags, float step0, float step, float hstep, uint32_t *__restrict__ undecided,
+                             int list_g) {
     const ViewArgs &A = VB.v[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, npix = A.Wb * A.Hb;
     const bool valid = i < npix;
@@ -76,7 +81,7 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
         flags[(size_t)blockIdx.y * npix + i] = (unsigned char)f;
     }
     if (undecided) {
-        const bool open = valid && !(f & (DSDF_PX_EMPTY | DSDF_PX_HIT));
+        const bool open = valid && (!(f & (DSDF_PX_EMPTY | DSDF_PX_HIT)) || (list_g && (f & 3u) == DSDF_PX_EMPTY));
         const uint64_t m = __ballot(open);
         if (m != 0) {
             const int leader = __builtin_ctzll(m);
@@ -88,14 +93,18 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
     }
 }
 
-// Second stage of the hit proof on the pixels k_pixel_skip left undecided: pixel_hit_proof (dsdf_proof.h) over the
-// full-resolution window maxima -- ~600 samples half a voxel apart per ray.  Inside k_pixel_skip that loop cost 1.2 ms per
+// Second stage of both proofs on the pixels k_pixel_skip listed.  First the empty-space proof, pixel_empty_proof itself over the
+// full-resolution window MINIMA (Bmin.b != nullptr): the block minima only prove a pixel whose rays stay 6-8 voxels clear of the
+// surface, these one whose rays stay about 3.  Its result goes to bit 7 (DSDF_PX_EMPTY_FINE) and bit 1, never to bit 0, which
+// keeps meaning "proven by the block minima".  Then, where that fails and the hit proof is wanted (hit), on the pixels without
+// bit 0, pixel_hit_proof (dsdf_proof.h) over the window maxima -- ~600 samples half a voxel apart per ray.  Inside k_pixel_skip that loop cost 1.2 ms per
 // 12-view step: a few undecided pixels per wave, each a serial chain on an otherwise idle wave; a wave-cooperative form (64
 // samples of one pixel per wave iteration, prefix maxima by shuffles) did MORE work, 1.7 ms.  So the undecided pixels are
 // COMPACTED (k_pixel_skip appends them to a list, one reservation per wave) and a dense launch runs the serial form, one pixel
 // per lane, every wave full.
-__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid B, dsdf_params P, ViewBatch VB, unsigned char *__restrict__ flags,
-                                                        const uint32_t *__restrict__ count, const uint32_t *__restrict__ list, float step) {
+__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bmin, BoundGrid B, dsdf_params P, ViewBatch VB,
+                                                        unsigned char *__restrict__ flags, const uint32_t *__restrict__ count,
+                                                        const uint32_t *__restrict__ list, float step, int hit) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *count) return;
     const uint32_t e = list[i], npix = (uint32_t)(VB.v[0].Wb * VB.v[0].Hb), view = e / npix, pix = e - view * npix;
@@ -103,10 +112,17 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid B,
     const int py = (int)(pix / (uint32_t)A.Wb), px = (int)(pix - (uint32_t)py * (uint32_t)A.Wb);
     const CamRay r = camera_ray(A.cam, P, (float)(px - DSDF_BORDER) + 0.5f, (float)(py - DSDF_BORDER) + 0.5f, A.W, A.H);
     const V3 d = r.d * rsqf(dot(r.d, r.d));
-    if (pixel_hit_proof(G, B, P, r.o, d, step)) flags[e] |= (unsigned char)DSDF_PX_HIT;
+    const unsigned f = flags[e];
+    unsigned add = 0u;
+    if (Bmin.b) {
+        const unsigned m = pixel_empty_proof(G, Bmin, P, r.o, d, step);
+        add = ((m & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m & DSDF_PX_EMPTY_G);
+    }
+    if (hit && !add && !(f & DSDF_PX_EMPTY)) add = pixel_hit_proof(G, B, P, r.o, d, step);
+    if (add) flags[e] = (unsigned char)(f | add);
 }
 
-// Bits 2/3 (DSDF_PX_FAR / _FAR_G): every film pixel within +-4 of this one carries bit 0 / bit 1.  A sample only splats into
+// Bits 2/3 (DSDF_PX_FAR / _FAR_G): every film pixel within +-4 of this one carries bit 0 or 7 (px_primal_empty) / bit 1.  A sample only splats into
 // pixels within +-2 of its own, and a film pixel's weight sum only matters if a value lands on it or a
 // backward lane reads its adjoint -- both need a pixel within +-2 of it that is NOT proven empty.  So the
 // samples of a pixel with bit 2 (3) set cannot influence any output of the primal (gradient) pass and are
@@ -127,7 +143,7 @@ __global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags) {
     for (int y = max(py - DSDF_FAR_RADIUS, 0); y <= min(py + DSDF_FAR_RADIUS, A.Hb - 1); ++y)
         for (int x = max(px - DSDF_FAR_RADIUS, 0); x <= min(px + DSDF_FAR_RADIUS, A.Wb - 1); ++x) {
             const unsigned v = f[y * A.Wb + x];
-            m &= v;
+            m &= v | (px_primal_empty(v) ? DSDF_PX_EMPTY : 0u);
             if (abs(y - py) <= 2 && abs(x - px) <= 2) near &= v;
         }
     f[i] = (unsigned char)((f[i] & DSDF_PX_KEEP) | ((m & 3u) << 2) | ((m & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near ? DSDF_PX_ONE : 0u));
@@ -138,19 +154,20 @@ __global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags) {
 // film pixel ALL of whose contributors (the pixels within +-2) are proven empty receives only samples of value `env`: it develops to
 // env whatever their weights are.  k_film_env adds (env, 1) to every such film pixel of the call's row window; the samples of a far
 // pixel (bit 2 / 3: everything within +-4 proven empty) only ever reach such film pixels and are not generated.  Where samples of
-// near pixels still arrive, (env + sum w env) / (1 + sum w) = env.  pass_bit: DSDF_PX_EMPTY (primal) or DSDF_PX_EMPTY_G (gradient pass:
-// its film is developed too, and no backward lane reads the adjoint of such a pixel).
+// near pixels still arrive, (env + sum w env) / (1 + sum w) = env.  pass_mask: a contributor counts as proven empty when it carries
+// one of these bits -- DSDF_PX_EMPTY | DSDF_PX_EMPTY_FINE (primal) or DSDF_PX_EMPTY_G (gradient pass: its film is developed too, and
+// no backward lane reads the adjoint of such a pixel).
 __global__ void k_film_env(ViewBatch VB, const unsigned char *__restrict__ flags, float *__restrict__ blocks, int row0, int row1,
-                           unsigned pass_bit, float er, float eg, float eb) {
+                           unsigned pass_mask, float er, float eg, float eb) {
     const ViewArgs &A = VB.v[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, npix = A.Wb * A.Hb;
     if (i >= npix) return;
     const int py = i / A.Wb, px = i - py * A.Wb;
     if (py < row0 || py >= row1) return;
     const unsigned char *f = flags + (size_t)blockIdx.y * npix;
-    unsigned m = pass_bit;
+    bool m = true;
     for (int y = max(py - 2, 0); y <= min(py + 2, A.Hb - 1); ++y)
-        for (int x = max(px - 2, 0); x <= min(px + 2, A.Wb - 1); ++x) m &= f[y * A.Wb + x];
+        for (int x = max(px - 2, 0); x <= min(px + 2, A.Wb - 1); ++x) m = m && (f[y * A.Wb + x] & pass_mask) != 0u;
     if (!m) return;
     float *b = blocks + ((size_t)blockIdx.y * npix + i) * 4;
     atomicAdd(b, er); atomicAdd(b + 1, eg); atomicAdd(b + 2, eb); atomicAdd(b + 3, 1.f);
@@ -181,7 +198,9 @@ static size_t padded_floats(int rx, int ry, int rz) {
 }
 
 // The library's grid buffer: [padded grid | per level: block minima, dilated block minima | block maxima, dilated block maxima]
-//                             [.. | fine window maxima, scratch | row-block copy of the padded grid (dsdf_math.h: DSDF_TLAYOUT)]
+//                             [.. | fine window maxima, fine window minima | row-block copy of the padded grid (dsdf_math.h: DSDF_TLAYOUT)]
+// (the minima live in what used to be the scratch of the maxima's passes; both sets of passes now ping-pong through the region of
+// the row-block copy BEFORE k_tlayout fills it -- a -DDSDF_TLAYOUT=0 build has no such region, keeps the scratch and has no minima)
 static size_t tlayout_offset(int rx, int ry, int rz);
 static GridView device_view(const float *padded, int rx, int ry, int rz, const dsdf_params &prm) {
     GridView G = make_view(padded, rx, ry, rz, prm);
@@ -210,7 +229,7 @@ static BoundGrid max_bounds(const float *padded, int rx, int ry, int rz) {
     B.b = c + hit_cells(rx, ry, rz);
     return B;
 }
-// [.. | block maxima, dilated | fine window maxima (rz,ry,rx) | scratch of the same size]
+// [.. | block maxima, dilated | fine window maxima (rz,ry,rx) | fine window minima (rz,ry,rx)]
 static float *fine_buffer(const float *padded, int rx, int ry, int rz) {
     const float *c = padded + padded_floats(rx, ry, rz);
     for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
@@ -227,5 +246,15 @@ static BoundGrid fine_bounds(const float *padded, int rx, int ry, int rz) {
     BoundGrid B;
     B.cx = rx; B.cy = ry; B.cz = rz; B.shift = 0; B.off = 0.5f;
     B.b = fine_buffer(padded, rx, ry, rz);
+    return B;
+}
+// The fine minima of the empty-space proof's second stage (b = nullptr: this build has none, the stage is off).
+static BoundGrid fine_min_bounds(const float *padded, int rx, int ry, int rz) {
+    BoundGrid B = fine_bounds(padded, rx, ry, rz);
+#if DSDF_TLAYOUT
+    B.b += (size_t)rx * ry * rz;
+#else
+    B.b = nullptr;
+#endif
     return B;
 }

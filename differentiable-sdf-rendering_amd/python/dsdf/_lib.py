@@ -16,6 +16,7 @@ DSDF_DIRECT = 2
 DSDF_REPARAM = 1
 DSDF_NO_SKIP = 2
 DSDF_NO_HIT_PROOF = 4
+DSDF_NO_FINE_EMPTY = 8
 
 
 class DsdfCamera(C.Structure):

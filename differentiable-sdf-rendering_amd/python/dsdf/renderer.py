@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (DSDF_DIRECT, DSDF_NO_HIT_PROOF, DSDF_NO_SKIP, DSDF_REPARAM, DSDF_SILHOUETTE, DSDF_SIMPLE_SHADING, DsdfCamera,
+from ._lib import (DSDF_DIRECT, DSDF_NO_FINE_EMPTY, DSDF_NO_HIT_PROOF, DSDF_NO_SKIP, DSDF_REPARAM, DSDF_SILHOUETTE, DSDF_SIMPLE_SHADING, DsdfCamera,
                    DsdfShading)
 
 INTEGRATORS = {'sdf_silhouette_reparam': DSDF_SILHOUETTE, 'sdf_simple_shading_reparam': DSDF_SIMPLE_SHADING,
@@ -30,9 +30,12 @@ _workspaces = {}
 
 
 def _proof_flags(empty_space_skip):
-    """True: both per-pixel proofs (csrc/dsdf_proof.h); 'empty-only': without the hit proof of the silhouette primal; False: none."""
+    """True: both per-pixel proofs (csrc/dsdf_proof.h); 'empty-only': without the hit proof of the silhouette primal; 'coarse-empty':
+    without the second stage of the empty-space proof on the full-resolution window minima (A/B and tests); False: none."""
     if empty_space_skip == 'empty-only':
         return DSDF_NO_HIT_PROOF
+    if empty_space_skip == 'coarse-empty':
+        return DSDF_NO_FINE_EMPTY
     return 0 if empty_space_skip else DSDF_NO_SKIP
 
 # Views traced by one kernel launch (bounded by the workspace: the backward queue of a GRADIENT pass holds 40 B per
@@ -701,7 +704,7 @@ def _lease_sweep_workspace(dev):
 
 
 def step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator=DSDF_SILHOUETTE, reparam=True, shading=None,
-               grad_albedo=None):
+               grad_albedo=None, empty_space_skip=True):
     """Forward half of one differentiable render step (python/shape_opt.py:77-80: `mi.render(..., seed, spp, seed_grad, spp_grad)`):
     returns (images, handle).  The forward sweep of the gradient pass (tracing, film, backward queue, the image-independent half
     of the adjoint: dsdf_grad_sweep) does not depend on the image gradient, so it is enqueued on a high-priority side stream
@@ -729,14 +732,15 @@ def step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator=DSDF_
         ws, lease = _lease_sweep_workspace(dev)
         with torch.cuda.stream(side):
             sweep = GradSweep(grid, sensors, spp_grad, (0, H + 4), seeds=seeds_grad, integrator=integrator, reparam=reparam,
-                              shading=shading, grad_albedo=grad_albedo, workspace=ws)
+                              shading=shading, grad_albedo=grad_albedo, workspace=ws, empty_space_skip=empty_space_skip)
             if sweep.ws is not None and sweep.ws is not ws:
                 if lease is not None:
                     lease['leased'] = False
                 # (a larger / first buffer: it becomes the cached one, owned by this step until step_finish)
                 lease = _sweep_workspaces[dev] = {'ws': sweep.ws, 'leased': True}
             film_g = sweep.sweep(new_film(len(sensors), W, H, integrator, dev))
-        img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading)
+        img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading,
+                             empty_space_skip=empty_space_skip)
     return img, StepHandle(sweep, film_g, main, side, lease)
 
 
@@ -764,18 +768,19 @@ def step_finish(handle, grad_image, grad_grid, grad_p=None):
 
 
 def render_step(grid, sensors, spp, spp_grad, loss_grad, grad_grid, seeds, seeds_grad, integrator=DSDF_SILHOUETTE, reparam=True,
-                shading=None, grad_albedo=None, grad_p=None, overlap=True):
+                shading=None, grad_albedo=None, grad_p=None, overlap=True, empty_space_skip=True):
     """One differentiable render step (python/shape_opt.py:77-83 for a batch of views): primal render at `spp`, image
     gradient `loss_grad(images)`, gradient pass at `spp_grad` accumulating into `grad_grid` -- the same three library calls as
     render_forward + render_backward, scheduled on TWO HIP streams (step_begin / step_finish): only the backward proper
     (dsdf_grad_backward) waits for both the primal image and the sweep.  Returns the images."""
     sensors = _as_list(sensors)
     if not overlap:
-        img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading)
+        img = render_forward(grid, sensors, spp, seeds=seeds, integrator=integrator, reparam=reparam, shading=shading,
+                             empty_space_skip=empty_space_skip)
         render_backward(grid, sensors, spp_grad, loss_grad(img), grad_grid=grad_grid, seeds=seeds_grad, integrator=integrator,
-                        reparam=reparam, shading=shading, grad_albedo=grad_albedo, grad_p=grad_p)
+                        reparam=reparam, shading=shading, grad_albedo=grad_albedo, grad_p=grad_p, empty_space_skip=empty_space_skip)
         return img
-    img, h = step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator, reparam, shading, grad_albedo)
+    img, h = step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator, reparam, shading, grad_albedo, empty_space_skip)
     step_finish(h, loss_grad(img), grad_grid, grad_p)
     return img
 

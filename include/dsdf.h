@@ -50,7 +50,9 @@ enum dsdf_integrator {
 enum dsdf_flags {
     DSDF_REPARAM = 1,
     DSDF_NO_SKIP = 2,        /* disable the exact per-pixel proofs (empty space and hit; A/B and testing) */
-    DSDF_NO_HIT_PROOF = 4    /* keep the empty-space proof, disable the hit proof of the silhouette primal (csrc/dsdf_proof.h) */
+    DSDF_NO_HIT_PROOF = 4,   /* keep the empty-space proof, disable the hit proof of the silhouette primal (csrc/dsdf_proof.h) */
+    DSDF_NO_FINE_EMPTY = 8   /* keep the proofs on the block bounds, disable the second stage of the empty-space proof on the
+                                full-resolution window minima (A/B and testing) */
 };
 
 /* Perspective sensor as built by python/util.py:115-138 (`get_regular_cameras`):
@@ -126,8 +128,11 @@ void        dsdf_default_params(dsdf_params *p);
  * footprint is always four contiguous 16-byte rows) followed by the bounds of the exact
  * per-pixel proofs (csrc/dsdf_proof.h): two coarse min-grids (8^3- and 4^3-voxel block minima
  * and their 3x3x3 dilations: pixels whose samples all MISS), a max-grid (2^3-voxel block maxima
- * and their 5x5x5 dilation) and the full-resolution window maxima with their scratch (pixels
- * whose samples all HIT; silhouette integrator).  2.2 x the grid + 5 %: 213 MiB at 256^3. */
+ * and their 5x5x5 dilation: pixels whose samples all HIT; silhouette integrator) and two full-resolution
+ * buffers, the window maxima (second stage of the hit proof) and the window minima (second stage of the
+ * empty-space proof, every integrator).  The minima occupy what used to be the scratch of the maxima's
+ * passes: dsdf_pad_grid now runs both sets of passes through the region of the row-block copy before it
+ * fills that region, so the size is unchanged.  2.2 x the grid + 5 %: 213 MiB at 256^3. */
 size_t dsdf_padded_size(int rx, int ry, int rz);
 
 /* Builds the padded copy.  Replaces `Texture3f.set_tensor` / `Grid3d.update`
@@ -361,7 +366,12 @@ int dsdf_set_grid_transform(const float *to_local, const float *aabb_lo, const f
  * bytes) -- a device buffer of at least n_views * (W+4) * (H+4) bytes -- the next render call of the calling thread writes its
  * flags there, and later calls with identical grid pointer, sizes, parameters and sensors read them (ordered by an event, on
  * whatever stream they run) instead of running the proof again.  dsdf_share_pixel_skip(NULL, 0) ends the bracket; the caller
- * must not update the grid inside it.  (No reference counterpart: Dr.Jit has no empty-space proof.) */
+ * must not update the grid inside it.  (No reference counterpart: Dr.Jit has no empty-space proof.)
+ * One byte per film-block pixel (csrc/dsdf_proof.h): bit 0 every sample of the primal misses, proven on the block minima; bit 1 ... and
+ * carries no boundary weight in the gradient pass (either stage); bits 2 / 3 the whole +-4 neighbourhood is proven empty for the
+ * primal / the gradient pass; bit 4 every sample hits; bits 5 / 6 its dilations; bit 7 every sample of the primal misses, proven by
+ * the second stage on the full-resolution window minima (never set together with a new bit 0: bit 0 keeps its meaning, a reader
+ * that wants "the primal misses" tests bit 0 OR bit 7).  DSDF_NO_FINE_EMPTY leaves bit 7 clear. */
 int dsdf_share_pixel_skip(void *buffer, size_t bytes);
 
 /* Measurement hook: after dsdf_kernel_timing_arm() the next render call of the calling thread (dsdf_render_forward /

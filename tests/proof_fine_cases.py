@@ -1,0 +1,90 @@
+"""Shared by tests/test_proof_fine_host.py and tests/test_gpu_proof_fine.py: the cases of the device-flag test
+(test_gpu_parity.py::test_device_proof_flags_match_host_proof) and the stand-alone host build of the second stage of the
+empty-space proof (tests/harness/dsdf_proof_fine_host.cpp)."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+import sdf_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_proof_fine_host.cpp')
+OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
+CASES = ['sphere64', 'blob64_flat', 'rag_x3']
+PX_EMPTY, PX_EMPTY_G, PX_HIT, PX_EMPTY_FINE = 1, 2, 16, 128
+ICAM, NCAM = 2, 5
+
+
+@functools.lru_cache(None)
+def host_lib():
+    os.makedirs(OUT, exist_ok=True)
+    out = os.path.join(OUT, 'libdsdf_proof_fine_host.so')
+    r = subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True)
+    assert r.returncode == 0, r.stdout
+    lib = C.CDLL(out)
+    lib.pfh_fine_empty.restype = C.c_float
+    return lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+@functools.lru_cache(None)
+def case(name):
+    """(grid (Z,Y,X) float32, W, H, camera origin) of one case."""
+    from cases import RAGGED, ragged_grid
+    from test_proof_host import _grids, RAGGED_FILMS
+    if name in RAGGED:
+        grid = ragged_grid(RAGGED[name][0], RAGGED[name][-1]).float().numpy()
+        W, H = RAGGED_FILMS[name][0]
+    else:
+        grid = _grids()[name]
+        W = H = 176
+    return np.ascontiguousarray(grid, np.float32), W, H, O.regular_camera_origins(NCAM)[ICAM]
+
+
+def fine_empty(params, grid, cam, W, H):
+    """flags (H+4, W+4) of pixel_empty_proof over the window minima (bits 0 / 1 as that function returns them), and its step."""
+    rz, ry, rx = grid.shape
+    flags = np.zeros((H + 4, W + 4), np.uint8)
+    cam = np.ascontiguousarray(cam, np.float32)
+    step = host_lib().pfh_fine_empty(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, _p(flags))
+    return flags, float(step)
+
+
+def sample_weights(params, grid, cam, W, H, spp, seed, mask):
+    """(H+4, W+4, spp) uint8 for the pixels of `mask`: bit 0 = the sample hits, bit 1 = its boundary weight is positive."""
+    rz, ry, rx = grid.shape
+    out = np.zeros((H + 4, W + 4, spp), np.uint8)
+    cam = np.ascontiguousarray(cam, np.float32)
+    mask = np.ascontiguousarray(mask, np.uint8)
+    host_lib().pfh_sample_weights(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, spp, C.c_uint(seed), _p(mask), _p(out))
+    return out
+
+
+def window_min(grid):
+    rz, ry, rx = grid.shape
+    out = np.zeros_like(grid)
+    host_lib().pfh_window_min(_p(grid), rx, ry, rz, _p(out))
+    return out
+
+
+_host_flags = {}
+
+
+def host_flags(harness, name):
+    """(coarse flags of the host harness, fine flags, info): computed once per case, shared by the tests, never modified."""
+    if name not in _host_flags:
+        grid, W, H, origin = case(name)
+        cam = O.Camera(origin).params()
+        coarse, info = harness.pixel_proof(grid, cam, W, H)
+        fine, fstep = fine_empty(harness.params, grid, cam, W, H)
+        assert fstep == info[3] > 0
+        coarse.setflags(write=False); fine.setflags(write=False)
+        _host_flags[name] = (coarse, fine, info)
+    return _host_flags[name]

@@ -5,7 +5,10 @@ only proves empty when its rays stay ~6-8 voxels away from the surface; the hit 
 maxima in round 4 (6^3 window).  This replays the mirror image -- window MINIMA over the taps [c - 2, c + 3]^3 of every B-spline cell --
 on one 512^2 view of the bench scene and weighs the pixels it would settle by the steps the fp32 C oracle needs for their rays.
 
-    python tools/sim_proofs.py [view] [spp]
+    python tools/sim_proofs.py [views, comma-separated: default 0,4,8] [spp]
+
+(the stage this replays is built -- csrc/dsdf_skip.h, k_pixel_hit_fine; the ratios printed here are the prediction its
+measurement is set against.)
 """
 import ctypes as C
 import os
@@ -41,8 +44,14 @@ def window_min(grid, lo=-2, hi=3):
 
 
 def main():
-    view = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+    views = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else '0,4,8').split(',')]
     spp = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    for view in views:
+        print(f'==== view {view}, {spp} samples per pixel', flush=True)
+        replay(view, spp)
+
+
+def replay(view, spp):
     res, W = 256, 512
     Wb = W + 4
     grid = synth_grid(res, 'cpu').numpy()
@@ -104,7 +113,18 @@ def main():
             tr = c_oracle.trace(lib, grid, oo.numpy(), dd.numpy(), mt.numpy(), diff=diff)
             steps[a:b] = tr['steps'].reshape(-1, spp)
             if diff:
-                need[a:b] = (tr['warp_weight'] > 0).reshape(-1, spp)
+                # the BOUNDARY weight (csrc/dsdf_math.h: warp_weight_positive), 1 - |v(x_warp)| / min(edge_eps * warp_t, bd) > 0 -- not
+                # tr['warp_weight'], the clamped weight sum of the march, which is positive for nearly every ray
+                wt = tr['warp_t'].astype(np.float64)
+                fin = np.isfinite(wt) & (tr['warp_weight'] > 0)
+                x = oo.numpy()[fin] + wt[fin, None] * dd.numpy()[fin]
+                v = np.asarray(c_oracle.eval_cubic(lib, grid, x)[0], np.float64).reshape(-1)
+                bd = np.maximum(0.0, np.minimum((x + prm.bbox_delta).min(1), (1 + prm.bbox_delta - x).min(1)))
+                eps = np.minimum(prm.edge_eps * wt[fin] if prm.weight_strategy == 6 else prm.edge_eps, bd)
+                w = np.zeros(len(wt), bool)
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    w[fin] = 1.0 - np.abs(v) / eps > 0
+                need[a:b] = w.reshape(-1, spp)
         return py, px, steps, need
 
     for name, now, then, diff in (('primal', ~empty & ~hit, ~empty2 & ~hit, False), ('sweep', ~empty_g, ~empty_g2, True)):
@@ -117,7 +137,7 @@ def main():
               f'wave-steps (max over {spp} samples) {wave} -> {wave2} ({wave2 / wave:.3f})   [{time.time() - t0:.0f}s]', flush=True)
         drop = ~keep
         if diff:
-            print(f'   dropped pixels holding a sample with warp weight > 0 (must be 0): {need[drop].any(1).sum()}')
+            print(f'   dropped pixels holding a sample with a boundary weight > 0 (must be 0): {need[drop].any(1).sum()}')
         else:
             print(f'   dropped pixels: max steps {steps[drop].max() if drop.any() else 0}, mean {steps[drop].mean() if drop.any() else 0:.1f}; '
                   f'kept: mean {steps[keep].mean():.1f}')
