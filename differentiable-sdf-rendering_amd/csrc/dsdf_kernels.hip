@@ -2017,4 +2017,5 @@ int dsdf_kernel_timing_read(float *ms) {
 
 #include "dsdf_redistance.h"
 #include "dsdf_bvh.h"
+#include "dsdf_iso.h"
 #include "dsdf_mesh.h"

@@ -236,9 +236,9 @@ DSDF_HD int iclamp(int v, int lo, int hi) {
 #endif
 }
 
-DSDF_HD CubicSetup cubic_setup(const GridView &G, V3 x) {
+// (the *_q forms take q already in the frame of the texture -- the cube's own coordinates: csrc/dsdf_iso.h)
+DSDF_HD CubicSetup cubic_setup_q(const GridView &G, V3 q) {
     // pf = (x - p) * res - 0.5 ; shapes.py:412 + Dr.Jit texel-centre convention
-    const V3 q = to_grid(G, x);
     float pfx = fmaf(q.x, G.frx, -0.5f);
     float pfy = fmaf(q.y, G.fry, -0.5f);
     float pfz = fmaf(q.z, G.frz, -0.5f);
@@ -251,6 +251,7 @@ DSDF_HD CubicSetup cubic_setup(const GridView &G, V3 x) {
     s.ix = (int)fx - 1; s.iy = (int)fy - 1; s.iz = (int)fz - 1;
     return s;
 }
+DSDF_HD CubicSetup cubic_setup(const GridView &G, V3 x) { return cubic_setup_q(G, to_grid(G, x)); }
 
 // 2-wide float vector (packed-fp32 VALU ops; v_pk_fma_f32 issues at half rate on the
 // SIMD-32 VALU, so it saves instruction slots, not FLOP time).
@@ -262,7 +263,7 @@ DSDF_HD v2f splat2(float a) { v2f r = {a, a}; return r; }
 // index clamped to [-3, r-1], see GridView) and the fractional offsets.
 struct CubicCell { uint32_t base; float ax, ay, az; };
 
-DSDF_HD CubicCell cubic_cell(const GridView &G, V3 x) {
+DSDF_HD CubicCell cubic_cell_q(const GridView &G, V3 q) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // Same cell as below in 3 instead of 6 instructions per axis: clamp(int(floor) - 1, -3, r - 1) + 3 == int(med3(floor, -2, r)) + 2;
     // the float clamp is exact (small integers) and swallows NaN / huge coordinates of masked lanes, the "+ 2" of the three
@@ -273,7 +274,6 @@ DSDF_HD CubicCell cubic_cell(const GridView &G, V3 x) {
     // swallowed like before) + an integer med3, and v_fract_f32 for the offset: 3 instead of 4 instructions per axis.  v_fract
     // returns x - floor(x) clamped below 1, which differs from the subtraction only for |x| < 2^-25 below an integer
     // (0.99999994 instead of 1.0 in the cell below -- the same spline value to 1e-7).
-    const V3 q = to_grid(G, x);
     const float pfx = fmaf(q.x, G.frx, -0.5f), pfy = fmaf(q.y, G.fry, -0.5f), pfz = fmaf(q.z, G.frz, -0.5f);
     CubicCell cc;
     cc.ax = __builtin_amdgcn_fractf(pfx); cc.ay = __builtin_amdgcn_fractf(pfy); cc.az = __builtin_amdgcn_fractf(pfz);
@@ -308,7 +308,7 @@ DSDF_HD CubicCell cubic_cell(const GridView &G, V3 x) {
     return cc;
 #endif
 #else
-    CubicSetup s = cubic_setup(G, x);
+    CubicSetup s = cubic_setup_q(G, q);
     int bx = iclamp(s.ix, -DSDF_APRON, G.rx - 1) + DSDF_APRON;
     int by = iclamp(s.iy, -DSDF_APRON, G.ry - 1) + DSDF_APRON;
     int bz = iclamp(s.iz, -DSDF_APRON, G.rz - 1) + DSDF_APRON;
@@ -318,6 +318,7 @@ DSDF_HD CubicCell cubic_cell(const GridView &G, V3 x) {
     return c;
 #endif
 }
+DSDF_HD CubicCell cubic_cell(const GridView &G, V3 x) { return cubic_cell_q(G, to_grid(G, x)); }
 
 // Row provider reading the 16 rows (k = z tap, j = y tap; four x-consecutive floats each)
 // of a cell straight from the padded grid: one 16-byte, 4-byte-aligned load per row with
@@ -350,7 +351,8 @@ DSDF_HD GlobalRows global_rows(const GridView &G, const CubicCell &c) {
 // A1: Grid3d.eval / eval_and_grad / eval_all (shapes.py:420-450) on the rows of one cell.
 // ORDER 0: v; 1: v,g; 2: v,g,H (xx,yy,zz,xy,xz,yz).  Gradient scaled by res,
 // Hessian by res_i*res_j (Dr.Jit eval_cubic_grad / eval_cubic_hessian).
-template <int ORDER, class Rows>
+// LOCAL (an XF build only): the derivatives stay in the frame of the texture.
+template <int ORDER, bool LOCAL = false, class Rows>
 DSDF_HD void eval_cubic_rows(const GridView &G, const CubicCell &c, const Rows &rows, float &v, V3 &g, float H[6]) {
     float wx[4], wy[4], wz[4];
     bspline_w(c.ax, wx); bspline_w(c.ay, wy); bspline_w(c.az, wz);
@@ -422,6 +424,7 @@ DSDF_HD void eval_cubic_rows(const GridView &G, const CubicCell &c, const Rows &
     }
 #if DSDF_XF
     // shapes.py:426-427, 445-448: gradient through to_local3^T, Hessian through to_local3^T H to_local3
+    if (LOCAL) return;
     if (ORDER >= 2) {
         // column j of A^T H A is A^T (H col_j(A))
         const V3 c0 = xf_apply_t(symmul(H, xf_col(0))), c1 = xf_apply_t(symmul(H, xf_col(1))), c2 = xf_apply_t(symmul(H, xf_col(2)));
@@ -435,6 +438,12 @@ template <int ORDER>
 DSDF_HD void eval_cubic(const GridView &G, V3 x, float &v, V3 &g, float H[6]) {
     CubicCell c = cubic_cell(G, x);
     eval_cubic_rows<ORDER>(G, c, global_rows(G, c), v, g, H);
+}
+// The same lookup at q in the cube's own coordinates with derivatives in that frame, whatever the build: no `sdf.p`, no to_local.
+template <int ORDER>
+DSDF_HD void eval_cubic_local(const GridView &G, V3 q, float &v, V3 &g, float H[6]) {
+    CubicCell c = cubic_cell_q(G, q);
+    eval_cubic_rows<ORDER, true>(G, c, global_rows(G, c), v, g, H);
 }
 
 // Fetch policy of the tracing loops.  DirectFetch: every lane reads its own rows (any ray

@@ -123,6 +123,7 @@ class SdfGrid:
         corners = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)])
         w = corners @ tw[:3, :3].T + tw[:3, 3]
         self.transform = (_floats(inv[:3, :].reshape(-1)), _floats(w.min(0)), _floats(w.max(0)))
+        self.to_world = tw
         return self
 
     _IDENTITY = None
@@ -889,6 +890,54 @@ def mesh_render(bvh, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SIL
         _lib.check(lib.dsdf_mesh_render_forward(_ptr(bvh.buffer), C.byref(prm), cams, nv, W, H, spp, _ptr(offsets), cseeds, integ, sh,
                                                 _ptr(img), _ptr(ws), ws.numel(), _stream()))
     return img
+
+
+def extract_mesh(grid, resolution=None, iso=0.0, steps=24, normals=True):
+    """Triangle mesh of the surface the renderer sees: the level set {f = iso} of the grid's tricubic lookup f, by marching tetrahedra
+    on a lattice of `resolution` (an int or (nx, ny, nz); default: the grid's own) cells, every vertex moved onto the root of f on its
+    lattice edge by `steps` bisection steps (include/dsdf.h: dsdf_iso_*, csrc/dsdf_iso.h) -> (vertices (V, 3) float32, faces (F, 3)
+    int32[, normals (V, 3)]) on the grid's device, in WORLD space: the library works in the cube's own frame, `+ sdf.p` and a general
+    to_world (normals through its inverse transpose) are applied here.  Faces wind so that their normal points towards larger f.
+    `vertices[faces.long()]` with `normals[faces.long()]` is what dsdf.MeshBvh takes.  A surface that leaves the cube stays open there;
+    no surface gives V = F = 0.  The two exclusive scans between the launches are torch.cumsum (plumbing), and their totals are read
+    back once to size the outputs -- the call synchronises there."""
+    lib = _lib.load()                                      # (cube coordinates in either build: the default one serves every grid)
+    if resolution is None:
+        nx, ny, nz = grid.rx, grid.ry, grid.rz
+    elif isinstance(resolution, (tuple, list)):
+        nx, ny, nz = (int(v) for v in resolution)
+    else:
+        nx = ny = nz = int(resolution)
+    dev = grid.device
+    N = (nx + 1) * (ny + 1) * (nz + 1) if min(nx, ny, nz) >= 1 else 1
+    iso_c = C.c_float(iso)
+    with torch.cuda.device(dev):
+        st = _stream()
+        values = torch.empty(N, dtype=torch.float32, device=dev)
+        _lib.check(lib.dsdf_iso_sample(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, nx, ny, nz, _ptr(values), st))
+        cross = torch.empty(N, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, N, dtype=torch.int32, device=dev)
+        _lib.check(lib.dsdf_iso_mark(_ptr(values), nx, ny, nz, iso_c, _ptr(cross), _ptr(counts[0]), _ptr(counts[1]), st))
+        # (one 1-D scan per count: a scan along the rows of a (2, N) tensor runs one block per row, 350 x slower at 256^3)
+        ends = torch.stack([torch.cumsum(counts[0], 0, dtype=torch.int32), torch.cumsum(counts[1], 0, dtype=torch.int32)])
+        V, F = (int(v) for v in ends[:, -1].tolist())
+        offsets = ends - counts
+        vert_edge = torch.empty(V, dtype=torch.int32, device=dev)
+        faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        pos = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        nrm = torch.empty(V, 3, dtype=torch.float32, device=dev) if normals else None
+        if V > 0:
+            _lib.check(lib.dsdf_iso_emit(_ptr(values), nx, ny, nz, iso_c, _ptr(cross), _ptr(offsets[0]), _ptr(offsets[1]), _ptr(vert_edge),
+                                         _ptr(faces), st))
+            _lib.check(lib.dsdf_iso_refine(_ptr(grid.padded), grid.rx, grid.ry, grid.rz, _ptr(values), nx, ny, nz, iso_c, _ptr(vert_edge), V,
+                                           int(steps), _ptr(pos), _ptr(nrm), st))
+    if grid.transform is not None:
+        tw = torch.as_tensor(grid.to_world, dtype=torch.float64, device=dev)
+        pos = (pos.double() @ tw[:3, :3].T + tw[:3, 3]).float()
+        if nrm is not None:
+            nrm = torch.nn.functional.normalize(nrm.double() @ torch.linalg.inv(tw[:3, :3]), dim=1).float()
+    pos = pos + torch.tensor([float(v) for v in grid.params.sdf_p], dtype=torch.float32, device=dev)
+    return (pos, faces, nrm) if normals else (pos, faces)
 
 
 def kernel_timing_arm():

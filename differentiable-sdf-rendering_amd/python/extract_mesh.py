@@ -1,0 +1,35 @@
+"""`python extract_mesh.py <file.vol> [-o out.ply|out.obj] [--res N] [--iso v]`: the triangle mesh of the surface the renderer sees in
+an SDF checkpoint (the `.vol` files optimize.py writes) -- dsdf.extract_mesh on util.read_vol, written by mesh_to_sdf.save_ply /
+save_obj with the vertex normals.  The mesh lives in the unit cube of the grid, like the SDF."""
+import argparse
+import os
+import sys
+
+import dsdf
+import mesh_to_sdf
+import util
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('vol', help='SDF grid as a Mitsuba volume file (one channel)')
+    ap.add_argument('-o', '--output', default=None, help='.ply (binary) or .obj; default: the input name with .ply')
+    ap.add_argument('--res', type=int, default=None, help="cells per axis of the extraction lattice (default: the grid's own resolution)")
+    ap.add_argument('--iso', type=float, default=0.0, help='level to extract (default 0)')
+    ap.add_argument('--steps', type=int, default=24, help='bisection steps per vertex (1 ... 32)')
+    args = ap.parse_args(argv)
+    out = args.output or os.path.splitext(args.vol)[0] + '.ply'
+    if not out.endswith(('.ply', '.obj')):
+        ap.error('the output must be a .ply or an .obj file')
+    data = util.read_vol(args.vol)
+    if data.dim() != 3:
+        ap.error(f'{args.vol}: expected a one-channel volume, got shape {tuple(data.shape)}')
+    grid = dsdf.SdfGrid(data.float().contiguous())
+    v, f, n = dsdf.extract_mesh(grid, resolution=args.res, iso=args.iso, steps=args.steps)
+    (mesh_to_sdf.save_obj if out.endswith('.obj') else mesh_to_sdf.save_ply)(out, v, f, n)
+    print(f'{out}: {v.shape[0]} vertices, {f.shape[0]} faces')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

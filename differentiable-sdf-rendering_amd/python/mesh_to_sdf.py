@@ -117,6 +117,49 @@ def load_ply(fn):
     return verts, np.asarray(faces, np.int64).reshape(-1, 3)
 
 
+def _mesh_arrays(vertices, faces, normals):
+    def host(a, dt):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return np.ascontiguousarray(a, dt).reshape(-1, 3)
+    v, f = host(vertices, '<f4'), host(faces, '<i4')
+    n = host(normals, '<f4') if normals is not None else None
+    if n is not None and n.shape != v.shape:
+        raise ValueError(f'normals must be (V, 3) like vertices, got {n.shape}')
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError('face index out of range')
+    return v, f, n
+
+
+def save_ply(fn, vertices, faces, normals=None):
+    """Writes an indexed triangle mesh (what dsdf.extract_mesh returns: tensors or arrays) as binary little-endian ply: x y z
+    [nx ny nz] per vertex, one uchar-counted int list per face.  load_ply reads it back."""
+    v, f, n = _mesh_arrays(vertices, faces, normals)
+    props = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if n is not None else [])
+    head = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + [f'property float {c}' for c in props] + \
+           [f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']
+    rec = np.zeros(len(f), np.dtype([('k', 'u1'), ('i', '<i4', (3,))]))
+    rec['k'] = 3
+    rec['i'] = f
+    with open(fn, 'wb') as fh:
+        fh.write(('\n'.join(head) + '\n').encode('ascii'))
+        fh.write((v if n is None else np.concatenate([v, n], 1)).astype('<f4').tobytes())
+        fh.write(rec.tobytes())
+    return fn
+
+
+def save_obj(fn, vertices, faces, normals=None):
+    """The same mesh as a Wavefront obj (v [vn] f, 1-based; 9 significant digits: float32 round-trips).  load_obj reads it back."""
+    v, f, n = _mesh_arrays(vertices, faces, normals)
+    with open(fn, 'w') as fh:
+        fh.writelines('v %.9g %.9g %.9g\n' % tuple(r) for r in v.tolist())
+        if n is not None:
+            fh.writelines('vn %.9g %.9g %.9g\n' % tuple(r) for r in n.tolist())
+            fh.writelines('f %d//%d %d//%d %d//%d\n' % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
+        else:
+            fh.writelines('f %d %d %d\n' % tuple(r) for r in (f + 1).tolist())
+    return fn
+
+
 def load_mesh_indexed(mesh_fn):
     """(V, 3) float32 vertices and (T, 3) faces; the plugin is chosen the way the reference does (mesh_to_sdf.py:12)."""
     v, f = load_obj(mesh_fn) if mesh_fn.endswith('.obj') else load_ply(mesh_fn)

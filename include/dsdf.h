@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DSDF_VERSION 308   /* 308 (additive, same number: no existing entry point or struct changed): dsdf_mesh_bvh_size, dsdf_mesh_morton, dsdf_mesh_bvh_build, dsdf_mesh_bvh_raycast, dsdf_mesh_render_workspace_size, dsdf_mesh_render_forward; 308: dsdf_cell_table_size, row-block copy in the grid buffer (dsdf_padded_size grew); 307: dsdf_tail_stats_arm; 300: stats rows of DSDF_STAT_SLOTS (16) counters; tail hand-off on library-owned helper streams; 304: DSDF_NO_HIT_PROOF, the grid buffer carries the bounds of the hit proof (dsdf_padded_size); 305: dsdf_params grows by normalize_warp_field, max_reparam_depth; 306: dsdf_render_aovs, dsdf_aov_workspace_size, dsdf_sampler_2d, dsdf_set_grid_transform / dsdf_has_grid_transform, dsdf_shading.bsdf_lobe_samples */
+#define DSDF_VERSION 308   /* 308 (additive, same number: no existing entry point or struct changed): dsdf_iso_sample, dsdf_iso_mark, dsdf_iso_emit, dsdf_iso_refine; 308 (additive likewise): dsdf_mesh_bvh_size, dsdf_mesh_morton, dsdf_mesh_bvh_build, dsdf_mesh_bvh_raycast, dsdf_mesh_render_workspace_size, dsdf_mesh_render_forward; 308: dsdf_cell_table_size, row-block copy in the grid buffer (dsdf_padded_size grew); 307: dsdf_tail_stats_arm; 300: stats rows of DSDF_STAT_SLOTS (16) counters; tail hand-off on library-owned helper streams; 304: DSDF_NO_HIT_PROOF, the grid buffer carries the bounds of the hit proof (dsdf_padded_size); 305: dsdf_params grows by normalize_warp_field, max_reparam_depth; 306: dsdf_render_aovs, dsdf_aov_workspace_size, dsdf_sampler_2d, dsdf_set_grid_transform / dsdf_has_grid_transform, dsdf_shading.bsdf_lobe_samples */
 #define DSDF_STAT_SLOTS 16
 
 enum dsdf_status {
@@ -444,6 +444,33 @@ size_t dsdf_mesh_render_workspace_size(int width, int height, int n_views);
 int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsdf_camera *cams, int n_views, int width, int height, int spp,
                              const float *offsets, const uint32_t *seeds, int integrator, const dsdf_shading *shading, float *image_out,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- triangle mesh of the rendered surface: the level set {f = iso} of the tricubic lookup f of dsdf_eval_cubic (csrc/dsdf_iso.h) ----
+ * Marching tetrahedra on a lattice of nx x ny x nz cells over the unit cube of the grid, IN THE CUBE'S OWN FRAME: `sdf.p` and a grid
+ * transform play no part in these four calls, in either build of the library (the caller maps the result out).
+ *   nodes   (i/nx, j/ny, k/nz), 0 <= i <= nx ...; node index (k (ny + 1) + j)(nx + 1) + i; N = (nx + 1)(ny + 1)(nz + 1) <= 2^27
+ *   inside  values[node] < iso (strict).  Everything but the vertex positions is an exact function of the buffer `values`.
+ *   edges   a node owns the edges towards its upper neighbours, type 0 +x, 1 +y, 2 +z, 3 +x+y, 4 +x+z, 5 +y+z, 6 +x+y+z; an edge with
+ *           exactly one inside end carries one vertex; vertices are ordered by owning node, then type; vert_edge = 8 node + type
+ *   faces   a cell (lower corner c) is cut into the six tetrahedra c, c + e_a, c + e_a + e_b, c + (1,1,1) of the axis orders xyz, xzy,
+ *           yxz, yzx, zxy, zyx; one or two triangles per mixed tetrahedron (csrc/dsdf_iso.h lists them), oriented so that
+ *           (B - A) x (C - A) points towards larger f; ordered by cell (node index of c), tetrahedron, listing
+ * A surface that leaves the cube is not capped: the mesh is open along the lattice border.
+ * Sequence: dsdf_iso_sample -> values (N floats); dsdf_iso_mark -> cross (N uint8: bit t = the edge of type t crosses), n_vert (N: 0..7),
+ * n_tri (N: 0..12; 0 for a node that is no cell corner); the CALLER scans both counts exclusively (plumbing, like the sort in front of
+ * dsdf_mesh_bvh_build) and reads the two totals to allocate; dsdf_iso_emit -> vert_edge (V), faces (F x 3 vertex ids; vert_edge and
+ * faces may be NULL when V = 0); dsdf_iso_refine -> positions (V x 3) and, unless NULL, normals (V x 3).
+ * dsdf_iso_refine: `steps` (1 ... 32) bisection steps on the edge a b of each vertex from the bracket s in [0, 1] given by the signs in
+ * `values`: sm = (s0 + s1) / 2, the half that keeps f(a + sm (b - a)) < iso on a's side; position a + ((s0 + s1) / 2)(b - a); normal =
+ * the normalised gradient of f there (a zero gradient: the unit edge direction towards the outside end).  n_vert = 0 returns DSDF_OK
+ * without a launch. */
+int dsdf_iso_sample(const float *padded, int rx, int ry, int rz, int nx, int ny, int nz, float *values, void *stream);
+int dsdf_iso_mark(const float *values, int nx, int ny, int nz, float iso, uint8_t *cross, int32_t *n_vert, int32_t *n_tri, void *stream);
+int dsdf_iso_emit(const float *values, int nx, int ny, int nz, float iso, const uint8_t *cross, const int32_t *vert_offset,
+                  const int32_t *tri_offset, int32_t *vert_edge /* V */, int32_t *faces /* F x 3 */, void *stream);
+int dsdf_iso_refine(const float *padded, int rx, int ry, int rz, const float *values, int nx, int ny, int nz, float iso,
+                    const int32_t *vert_edge, int64_t n_vert, int steps, float *positions /* V x 3 */, float *normals /* V x 3 or NULL */,
+                    void *stream);
 
 #ifdef __cplusplus
 }
