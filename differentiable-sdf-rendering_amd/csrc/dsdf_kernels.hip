@@ -959,7 +959,7 @@ struct Workspace {
     uint32_t *count, *qlane;
     float *qrec, *qcoef;   // qcoef: DSDF_COEF_WORDS rows per queue slot (split backward; not for sdf_direct_reparam)
     uint32_t *count0;      // per unit: the queue length when the render kernel was done (k_backward_coef's two launches)
-    unsigned char *skip;
+    unsigned char *skip;   // two planes: the proof's flags, the effective plane of the third proof stage
     uint32_t *items;       // work lists of the persistent render kernel: DSDF_MAX_GROUPS headers, then one entry per film-block pixel and view
     char *tail;            // tail hand-off queues: DSDF_MAX_GROUPS x (counters | march states)
     size_t tail_bytes;
@@ -984,7 +984,7 @@ static Workspace carve(void *base, int W, int H, int spp, int nv, int integrator
     size_t off = 0;
     char *p = (char *)base;
     ws.block = (float *)(p + off); off += align_up(nv * Wb * Hb * nch * sizeof(float), 256);
-    ws.skip = (unsigned char *)(p + off); off += align_up(nv * Wb * Hb, 256);
+    ws.skip = (unsigned char *)(p + off); off += align_up(2 * nv * Wb * Hb, 256);
     ws.items = (uint32_t *)(p + off); off += align_up((DSDF_MAX_GROUPS * DSDF_ITEM_HDR + nv * Wb * Hb) * sizeof(uint32_t), 256);
     ws.block_adj = nullptr; ws.count = nullptr; ws.qlane = nullptr; ws.qrec = nullptr; ws.qcoef = nullptr; ws.coef_rows = 0; ws.count0 = nullptr;
     ws.tail = nullptr; ws.tail_bytes = 0; ws.tail_cap_sub = 0; ws.tail_words = 0; ws.hit_t = nullptr; ws.shq = nullptr; ws.shq_cap_sub = 0;
@@ -1239,6 +1239,12 @@ int dsdf_pad_grid(const float *data, int rx, int ry, int rz, float *padded, void
                            1 << DSDF_HIT_SHIFT);
         hipLaunchKernelGGL(k_coarse_dilate<true>, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, c0, c1, cx, cy, cz, DSDF_HIT_RADIUS);
     }
+    if (float *D = grad_bound(padded, rx, ry, rz)) {
+        // the third proof stage's gradient bound, in the undilated block maxima the dilation above has just consumed (dsdf_skip.h)
+        if (hipMemsetAsync(D, 0, 3 * sizeof(float), (hipStream_t)stream) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(gradient bound) failed");
+        const unsigned g = (unsigned)((size_t)ry * rz < 4096 ? (size_t)ry * rz : 4096);
+        hipLaunchKernelGGL(k_tap_diff_max, dim3(g), dim3(256), 0, (hipStream_t)stream, data, rx, ry, rz, (int *)D);
+    }
     {   // fine window maxima F and minima S, three separable passes each (x, y, z)
         float *F = fine_buffer(padded, rx, ry, rz), *S = F + (size_t)rx * ry * rz;
         const size_t total = (size_t)rx * ry * rz;
@@ -1437,6 +1443,7 @@ struct SkipShare {
     int rx = 0, ry = 0, rz = 0, W = 0, H = 0, nv = 0;
     int hit_proof = 0;     // the flags carry DSDF_PX_HIT (silhouette integrator, hit proof not disabled)
     int fine_empty = 0;    // the flags carry the second stage of the empty-space proof (bit 7, more of bit 1)
+    int value_bound = 0;   // the second half of the buffer is the effective plane of the third stage: the render stages read that
     dsdf_params prm;
     dsdf_camera cams[DSDF_MAX_BATCH];
 };
@@ -1446,6 +1453,7 @@ static bool skip_share_matches(const SkipShare &h, const PassCtx &c, const dsdf_
     return h.valid && h.padded == c.padded && h.rx == c.rx && h.ry == c.ry && h.rz == c.rz && h.W == c.W && h.H == c.H && h.nv == nv &&
            h.hit_proof <= (int)(c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF)) &&      // (flags WITHOUT hit bits serve any call)
            h.fine_empty <= (int)!(c.flags & DSDF_NO_FINE_EMPTY) &&                                         // (and so do flags without the fine stage)
+           h.value_bound <= (int)!(c.flags & (DSDF_NO_FINE_EMPTY | DSDF_NO_VALUE_BOUND)) &&                // (or without the third)
            memcmp(&h.prm, c.prm, sizeof(dsdf_params)) == 0 && memcmp(h.cams, cams, (size_t)nv * sizeof(dsdf_camera)) == 0;
 }
 
@@ -1465,7 +1473,7 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     const bool can_share = sh.buf && sh.ready && sh.bytes >= (size_t)nv * npix;
     if (can_share && skip_share_matches(sh, c, cams, nv)) {
         if (hipStreamWaitEvent(st, sh.ready, 0) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipStreamWaitEvent(shared skip flags) failed");
-        skip = sh.buf;
+        skip = sh.value_bound ? sh.buf + (size_t)nv * npix : sh.buf;
         return DSDF_OK;
     }
     unsigned char *dst = (can_share && !sh.valid) ? sh.buf : ws.skip;       // (a second, different batch keeps its own flags)
@@ -1479,6 +1487,14 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     const bool fine = fstep > 0.f && (want_hit || fmin.b);
     // (a gradient pass reads these flags -- this call, or a later one of the bracket: the pixels with bit 0 but not bit 1 are listed too)
     const int list_g = (fmin.b && (c.diff || dst == sh.buf)) ? 1 : 0;
+    // the third stage (dsdf_proof.h: ValueBound) rides on the second; its results go to the effective plane behind the flags -- in a
+    // caller's shared buffer only when that holds two planes, otherwise the stage is off for the bracket
+    ValueBound vb = {nullptr, 0.f};
+    if (fine && fmin.b && !(c.flags & DSDF_NO_VALUE_BOUND) && (dst != sh.buf || sh.bytes >= 2 * (size_t)nv * npix)) {
+        vb.D = grad_bound(c.padded, c.rx, c.ry, c.rz);
+        vb.r = value_bound_reach(cams, nv, c.W, c.rx, c.ry, c.rz, fstep);
+    }
+    unsigned char *plane = vb.D ? dst + (size_t)nv * npix : nullptr;
     // the pixels neither proof settles are listed in the (not yet built) work-list area of this workspace for the second
     // stage: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
     uint32_t *und = fine ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
@@ -1487,21 +1503,22 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     const float step0 = level > 0 ? skip_step(cams, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
     const dim3 pgrid((unsigned)((npix + 255) / 256), nv), blk(256);
     if ((rc = launch("k_pixel_skip", k_pixel_skip, pgrid, blk, st, device_view(c), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
-                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und, list_g)))
+                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und, list_g, plane)))
         return rc;
     if (und && (rc = launch("k_pixel_hit_fine", k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), blk, st, device_view(c),
-                            fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))
+                            fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), vb, c.pp, VB, dst, plane, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))
         return rc;
-    if ((rc = launch("k_skip_dilate", k_skip_dilate, pgrid, blk, st, VB, dst))) return rc;
+    if ((rc = launch("k_skip_dilate", k_skip_dilate, pgrid, blk, st, VB, dst, plane))) return rc;
     if (dst == sh.buf) {
         if (hipEventRecord(sh.ready, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipEventRecord(shared skip flags) failed");
         sh.valid = true; sh.padded = c.padded; sh.rx = c.rx; sh.ry = c.ry; sh.rz = c.rz; sh.W = c.W; sh.H = c.H; sh.nv = nv;
         sh.hit_proof = (int)want_hit;
         sh.fine_empty = (int)(fine && fmin.b);
+        sh.value_bound = (int)(plane != nullptr);
         sh.prm = *c.prm;
         memcpy(sh.cams, cams, (size_t)nv * sizeof(dsdf_camera));
     }
-    skip = dst;
+    skip = plane ? plane : dst;       // (the render stages read the effective plane where there is one)
     return DSDF_OK;
 }
 

@@ -10,6 +10,8 @@
 //     -- in two stages: on the dilated block minima (bits 0 / 1), then, for the pixels those leave, on full-resolution window
 //     minima (bits 7 / 1: hit_step_fine, k_pixel_hit_fine).  Bit 0 keeps meaning "proven by the BLOCK minima"; a reader that wants
 //     "the primal's samples all miss" asks px_primal_empty;
+//     -- and a third stage for both proofs: the spline value on the centre ray -+ a gradient bound (ValueBound, below), whose results
+//     go to a library-private effective plane with the same bit meanings, never to the byte a caller can read;
 //   * hit proof (bit 4, silhouette primal): see pixel_hit_proof -> every sample HITS.  The silhouette integrator consumes
 //     only the hit flag (sdf_silhouette_reparam.py:20-22), so such a pixel needs no march at all.
 // Both are proofs, not approximations: a flagged pixel gets exactly the flags tracing would produce
@@ -120,6 +122,117 @@ DSDF_HD unsigned pixel_hit_proof(const GridView &G, const BoundGrid &B, const ds
     return 0u;
 }
 
+// ---- Third stage: the exact spline value on the centre ray, minus / plus a gradient bound.
+// Each gradient component of a tricubic B-spline is a convex combination of differences of ADJACENT taps (cubic weights across the
+// axis, quadratic B-spline weights along it: all >= 0, sum 1; clamped taps repeat, their differences are 0).  With D_a the largest
+// |difference| along axis a (value per voxel) over the whole grid -- tools/sim_gradient_bound.py: a per-block D_a removes 2 % more of
+// the primal's lock-step iterations, not worth a lookup -- every y within r voxels of a centre-ray point x has
+//     |v(y) - v(x)| <= r |(D_x, D_y, D_z)|_2                                  (mean value theorem + Cauchy-Schwarz)
+// and r = lateral deviation + half a step is what the window bounds cover too (hit_step_fine: < 1 voxel).  Where a window bound of
+// the second stage fails its threshold, v(x) -+ margin replaces it in the UNCHANGED logic of pixel_empty_proof / pixel_hit_proof:
+// the window bound sits 3-5 voxels from the value on the ray, this one 1-1.7.
+// fp32 slack, all of it on the safe side:  (i) r carries 0.01 voxel for the rounding of x * res and of x = o + t d (|x| < 4:
+// 2.4e-7 * res < 0.01 voxel up to res = 4e4), like the window stage;  (ii) eval_value sums 64 products through three levels of
+// four-term fma chains with weights good to a few ulp: |error| < 32 ulp (1.9e-6) of the largest |tap| it reads.  v is a convex
+// combination of those 4^3 taps, so it lies between their extremes, and two of them are at most three tap steps apart per axis:
+// every |tap| <= |v| + 3 (D_x + D_y + D_z) -- 4e-6 (|v| + 3 |D|_1);  (iii) D and its norm are rounded: (1 + 1e-5).
+struct ValueBound {
+    const float *D;    // largest |tap difference| along x, y, z (k_tap_diff_max), nullptr: the stage is off
+    float r;           // voxels: lateral deviation + half a step + 0.01 (value_bound_reach)
+};
+struct ValueMargin { float L, tap; };      // margin(v) = L + 4e-6 (|v| + tap)
+DSDF_HD ValueMargin value_margin(const ValueBound &vb) {
+    const float dn = sqrtf(vb.D[0] * vb.D[0] + vb.D[1] * vb.D[1] + vb.D[2] * vb.D[2]);
+    ValueMargin m;
+    m.L = vb.r * dn * (1.f + 1e-5f);
+    m.tap = 3.f * (vb.D[0] + vb.D[1] + vb.D[2]);
+    return m;
+}
+
+struct HitRun {         // pixel_hit_proof's state between samples
+    float J, Jrun;
+    bool in_run, done;
+};
+DSDF_HD void hit_run_step(HitRun &s, float U, float tc, float half, bool inside) {
+    if (s.done) return;
+    if (U < 0.f && inside) {
+        if (!s.in_run) { s.in_run = true; s.Jrun = s.J; }
+        if (tc + half >= s.Jrun + 1e-4f) { s.done = true; return; }
+    } else s.in_run = false;
+    s.J = fmaxf(s.J, tc + half + U);
+}
+
+// Second and third stage of one listed pixel in ONE loop over the sample positions both proofs share (they start at the same t0 with
+// the same step): low byte = what `Bmin.b ? pixel_empty_proof(Bmin) : 0`, and where that is 0 and want_hit, pixel_hit_proof(Bmax)
+// return (tests/test_proof_value_host.py compares); bits 8.. = the same with the bounds tightened by the spline value (0 without
+// vb.D or without the window minima).  The third stage proves whatever the second proves -- its bounds are never looser, and a run
+// of the hit proof can only start earlier with a smaller landing bound -- so the loop ends when the third stage's minimum is at the
+// primal threshold and the second stage's hit proof is decided.  The value is evaluated only where the window straddles what it
+// has to clear (see the loop).
+DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, const BoundGrid &Bmax, const ValueBound &vb, const dsdf_params &P,
+                                   V3 o, V3 d, float step, bool want_hit) {
+    BoxHit b = bbox_ray_intersect(-P.bbox_delta - DSDF_PROOF_GROW, 1.f + P.bbox_delta + DSDF_PROOF_GROW, o, d);
+    if (!(b.hit && b.maxt > 0.f)) return 0u;
+    BoxHit in = bbox_ray_intersect(-P.bbox_delta + DSDF_PROOF_GROW, 1.f + P.bbox_delta - DSDF_PROOF_GROW, o, d);
+    want_hit = want_hit && P.trace_eps > 0.f && in.hit && in.maxt > 0.f;
+    const bool want_empty = Bmin.b != nullptr, third = want_empty && vb.D != nullptr;
+    const float t0 = fmaxf(b.mint, 0.f), t1 = b.maxt, half = 0.5f * step;
+    const float i0 = fmaxf(in.mint, 0.f), i1 = in.maxt;
+    const float thr_p = 2.f * P.trace_eps * fmaxf(t1, 1.f) + 1e-5f;
+    const float thr_g = (P.weight_strategy == 6 ? P.edge_eps * (t1 + 0.1f) : P.edge_eps) * 1.05f + 1e-4f;
+    const float thr_hi = fmaxf(thr_p, thr_g);
+    ValueMargin mg = {0.f, 0.f};
+    if (third) mg = value_margin(vb);
+    float m2 = INFINITY, m3 = INFINITY;
+    HitRun h2 = {-INFINITY, 0.f, false, false}, h3 = h2;
+    bool e_alive = want_empty;
+    for (float tb = t0; tb < t1 + step && (e_alive || (want_hit && !h2.done)); tb += 4.f * step) {
+        float tc[4], lo[4], hi[4], lo3[4], hi3[4];
+        const bool v_alive = third && (e_alive || (want_hit && !h3.done));
+        const bool fetch_lo = e_alive || v_alive;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool live = tb + (float)k * step < t1 + step;
+            tc[k] = fminf(tb + (float)k * step, t1);
+            const V3 x = fma3(tc[k], d, o);
+            lo3[k] = lo[k] = fetch_lo && live ? bound_at(Bmin, G, x) : INFINITY;
+            hi3[k] = hi[k] = want_hit ? bound_at(Bmax, G, x) : INFINITY;
+            // (the value can only matter where the window minimum fails the threshold still in play -- the larger one until the
+            // gradient flag is lost, then the primal's -- or, for the hit proof, where v + margin < 0 is possible: minimum < -margin
+            // under a maximum >= 0)
+            const bool need_e = e_alive && lo[k] <= (m3 > thr_hi ? thr_hi : thr_p);
+            const bool need_h = want_hit && !h3.done && hi[k] >= 0.f && lo[k] < -mg.L;
+            if (v_alive && live && (need_e || need_h)) {
+                const float v = eval_value(G, x), m = mg.L + 4e-6f * (fabsf(v) + mg.tap);
+                lo3[k] = fmaxf(lo[k], v - m);
+                hi3[k] = fminf(hi[k], v + m);
+            }
+        }
+        m2 = fminf(m2, fminf(fminf(lo[0], lo[1]), fminf(lo[2], lo[3])));
+        m3 = fminf(m3, fminf(fminf(lo3[0], lo3[1]), fminf(lo3[2], lo3[3])));
+        if (want_hit) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!(tb + (float)k * step < t1 + step)) break;
+                const bool inside = tc[k] - half >= i0 && tc[k] + half <= i1;
+                hit_run_step(h2, hi[k], tc[k], half, inside);
+                hit_run_step(h3, hi3[k], tc[k], half, inside);
+            }
+        }
+        e_alive = want_empty && m3 > thr_p;
+    }
+    unsigned f2 = 0u, f3 = 0u;
+    if (want_empty) {
+        if (m2 > thr_p) f2 |= DSDF_PX_EMPTY;
+        if (m2 > thr_hi) f2 |= DSDF_PX_EMPTY_G;
+        if (m3 > thr_p) f3 |= DSDF_PX_EMPTY;
+        if (m3 > thr_hi) f3 |= DSDF_PX_EMPTY_G;
+    }
+    if (!f2 && want_hit && h2.done) f2 = DSDF_PX_HIT;
+    if (!f3 && want_hit && h3.done) f3 = DSDF_PX_HIT;
+    return third ? (f2 | (f3 << 8)) : f2;
+}
+
 }  // namespace dsdf
 
 // ---- host side: block sizes and the margins under which the proofs hold (shared with the CPU tests through tests/harness)
@@ -197,6 +310,13 @@ static float hit_step_fine(const dsdf_camera *cams, int nv, int W, int rx, int r
     if (step_vox < 0.25f) return 0.f;
     if (step_vox > 1.f) step_vox = 1.f;
     return step_vox / (float)rmax;
+}
+
+// The r of the third stage's gradient bound (ValueBound, voxels) at the step of hit_step_fine: lateral deviation + half a step +
+// 0.01 voxel of rounding slack -- at most 1, since hit_step_fine keeps lateral deviation + half a step within 0.99.
+static float value_bound_reach(const dsdf_camera *cams, int nv, int W, int rx, int ry, int rz, float fstep) {
+    int rmax = rx > ry ? (rx > rz ? rx : rz) : (ry > rz ? ry : rz);
+    return pixel_spread_voxels(cams, nv, W, rmax) + 0.5f * fstep * (float)rmax + 0.01f;
 }
 
 // March step (world units) of the hit proof, or 0 when its margins are not covered: the dilation (DSDF_HIT_RADIUS blocks of

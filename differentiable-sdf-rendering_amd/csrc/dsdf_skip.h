@@ -55,8 +55,36 @@ __global__ void k_window(const float *__restrict__ in, float *__restrict__ out, 
     out[i] = m;
 }
 
+// The gradient bound of the third proof stage (dsdf_proof.h: ValueBound): D[a] = the largest |difference of adjacent taps| along x, y, z
+// over the whole grid.  D is zeroed by the caller; non-negative floats order like their bit patterns, so the maximum is an integer one.
+__global__ __launch_bounds__(256) void k_tap_diff_max(const float *__restrict__ data, int rx, int ry, int rz, int *__restrict__ D) {
+    float mx = 0.f, my = 0.f, mz = 0.f;
+    // (one row of x per block and turn: no 64-bit division per voxel)
+    for (int row = blockIdx.x; row < ry * rz; row += gridDim.x) {
+        const int y = row % ry, z = row / ry;
+        const float *r = data + (size_t)row * rx;
+        for (int x = threadIdx.x; x < rx; x += blockDim.x) {
+            const float v = r[x];
+            if (x + 1 < rx) mx = fmaxf(mx, fabsf(r[x + 1] - v));
+            if (y + 1 < ry) my = fmaxf(my, fabsf(r[x + (size_t)rx] - v));
+            if (z + 1 < rz) mz = fmaxf(mz, fabsf(r[x + (size_t)rx * ry] - v));
+        }
+    }
+    // (thousands of atomics on three addresses would cost more than the pass over the grid: one wave per block reduces the block's
+    // maxima and issues an atomic only for a value above what is stored -- D only grows)
+    __shared__ int part[4][3];
+    const int ix = wave_max_i32(__float_as_int(mx)), iy = wave_max_i32(__float_as_int(my)), iz = wave_max_i32(__float_as_int(mz));
+    if (lane_id() == 0) { part[threadIdx.x >> 6][0] = ix; part[threadIdx.x >> 6][1] = iy; part[threadIdx.x >> 6][2] = iz; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int m = max(max(part[0][threadIdx.x], part[1][threadIdx.x]), max(part[2][threadIdx.x], part[3][threadIdx.x]));
+        if (m > __atomic_load_n(D + threadIdx.x, __ATOMIC_RELAXED)) atomicMax(D + threadIdx.x, m);
+    }
+}
+
 // flags[view][Hb*Wb]: DSDF_PX_EMPTY / _EMPTY_G / _HIT of every film-block pixel (dsdf_proof.h).  step == 0: no empty-space
 // proof, hstep == 0: no hit proof (margins not covered, or the integrator consumes more than the hit flag).
+// `plane` (optional): the effective plane of the third stage (k_skip_dilate), cleared here.
 // `undecided` (optional): [0] = counter (zeroed by the caller), entries from [DSDF_UNDECIDED_HDR]: view * Wb * Hb + pixel of every
 // pixel neither proof settled -- the work list of k_pixel_hit_fine -- and, with list_g (a gradient pass will read these flags and
 // the fine empty-space stage runs), of every pixel with bit 0 but not bit 1: the fine minima may still give it bit 1.
@@ -65,7 +93,7 @@ __global__ void k_window(const float *__restrict__ in, float *__restrict__ out, 
 // as long): most pixels of a silhouette view pass far from the shape and are settled there.
 __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundGrid Bmax, dsdf_params P, ViewBatch VB,
                              unsigned char *__restrict__ flags, float step0, float step, float hstep, uint32_t *__restrict__ undecided,
-                             int list_g) {
+                             int list_g, unsigned char *__restrict__ plane) {
     const ViewArgs &A = VB.v[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, npix = A.Wb * A.Hb;
     const bool valid = i < npix;
@@ -79,6 +107,7 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
         if (f != (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G) && step > 0.f) f |= pixel_empty_proof(G, Bmin, P, r.o, d, step);
         if (hstep > 0.f && !(f & DSDF_PX_EMPTY)) f |= pixel_hit_proof(G, Bmax, P, r.o, d, hstep);
         flags[(size_t)blockIdx.y * npix + i] = (unsigned char)f;
+        if (plane) plane[(size_t)blockIdx.y * npix + i] = 0;         // (k_pixel_hit_fine adds what the third stage proves)
     }
     if (undecided) {
         const bool open = valid && (!(f & (DSDF_PX_EMPTY | DSDF_PX_HIT)) || (list_g && (f & 3u) == DSDF_PX_EMPTY));
@@ -102,9 +131,14 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
 // samples of one pixel per wave iteration, prefix maxima by shuffles) did MORE work, 1.7 ms.  So the undecided pixels are
 // COMPACTED (k_pixel_skip appends them to a list, one reservation per wave) and a dense launch runs the serial form, one pixel
 // per lane, every wave full.
-__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bmin, BoundGrid B, dsdf_params P, ViewBatch VB,
-                                                        unsigned char *__restrict__ flags, const uint32_t *__restrict__ count,
-                                                        const uint32_t *__restrict__ list, float step, int hit) {
+// Third stage (vb.D != nullptr, plane != nullptr), in the same loop: where a window bound fails, the spline value on the centre ray
+// -+ a gradient bound (dsdf_proof.h: ValueBound).  What it proves beyond the second stage goes to `plane`, the library-private
+// effective plane, with the same bit meanings (7 / 1 / 4); `flags`, which a caller may read, is written byte for byte as without it.
+// (As a launch of its own over the pixels the second stage leaves it cost 1.0 + 1.6 ms per proof instead of 1.9: DESIGN 5.61.)
+__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bmin, BoundGrid B, ValueBound vb, dsdf_params P, ViewBatch VB,
+                                                        unsigned char *__restrict__ flags, unsigned char *__restrict__ plane,
+                                                        const uint32_t *__restrict__ count, const uint32_t *__restrict__ list, float step,
+                                                        int hit) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *count) return;
     const uint32_t e = list[i], npix = (uint32_t)(VB.v[0].Wb * VB.v[0].Hb), view = e / npix, pix = e - view * npix;
@@ -113,13 +147,14 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bm
     const CamRay r = camera_ray(A.cam, P, (float)(px - DSDF_BORDER) + 0.5f, (float)(py - DSDF_BORDER) + 0.5f, A.W, A.H);
     const V3 d = r.d * rsqf(dot(r.d, r.d));
     const unsigned f = flags[e];
-    unsigned add = 0u;
-    if (Bmin.b) {
-        const unsigned m = pixel_empty_proof(G, Bmin, P, r.o, d, step);
-        add = ((m & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m & DSDF_PX_EMPTY_G);
-    }
-    if (hit && !add && !(f & DSDF_PX_EMPTY)) add = pixel_hit_proof(G, B, P, r.o, d, step);
+    // both stages, both proofs, one loop over the sample positions (dsdf_proof.h); the hit proof only for the pixels without bit 0
+    const unsigned m = pixel_fine_proofs(G, Bmin, B, vb, P, r.o, d, step, hit && !(f & DSDF_PX_EMPTY));
+    const unsigned m2 = m & 0xffu, m3 = m >> 8;
+    const unsigned add = ((m2 & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m2 & (DSDF_PX_EMPTY_G | DSDF_PX_HIT));
     if (add) flags[e] = (unsigned char)(f | add);
+    // the third stage's results never reach the caller-visible byte: the render stages read them from the effective plane
+    const unsigned add3 = ((m3 & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m3 & (DSDF_PX_EMPTY_G | DSDF_PX_HIT));
+    if (plane && add3) plane[e] = (unsigned char)add3;
 }
 
 // Bits 2/3 (DSDF_PX_FAR / _FAR_G): every film pixel within +-4 of this one carries bit 0 or 7 (px_primal_empty) / bit 1.  A sample only splats into
@@ -133,20 +168,31 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bm
 // weight channel and it develops to 1 whatever the samples are (bit 6); a pixel whose whole +-4 neighbourhood carries
 // DSDF_PX_HIT only ever feeds such film pixels, so its samples are not generated (bit 5) -- k_film_ones adds (1, 1) to every
 // bit-6 film pixel instead, which leaves value == weight where samples still arrive and gives 1 / 1 where none does.
-__global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags) {
+// `plane` (optional, the third stage's effective plane): holds the KEEP bits the third stage ADDS (k_pixel_hit_fine); this pass completes
+// it to what the render stages read -- the KEEP bits of flags | plane and bits 2 / 3 / 5 / 6 recomputed from those -- in the same
+// sweep over the neighbourhood.  In place like `flags`: a neighbour already rewritten holds flags' KEEP bits too, the same union.
+__global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags, unsigned char *__restrict__ plane) {
     const ViewArgs &A = VB.v[blockIdx.y];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.Wb * A.Hb) return;
     unsigned char *f = flags + (size_t)blockIdx.y * A.Wb * A.Hb;
+    unsigned char *p = plane ? plane + (size_t)blockIdx.y * A.Wb * A.Hb : nullptr;
     int py = i / A.Wb, px = i - py * A.Wb;
-    unsigned m = 3u | DSDF_PX_HIT, near = DSDF_PX_HIT;
+    unsigned m = 3u | DSDF_PX_HIT, near = DSDF_PX_HIT, m3 = m, near3 = near;
     for (int y = max(py - DSDF_FAR_RADIUS, 0); y <= min(py + DSDF_FAR_RADIUS, A.Hb - 1); ++y)
         for (int x = max(px - DSDF_FAR_RADIUS, 0); x <= min(px + DSDF_FAR_RADIUS, A.Wb - 1); ++x) {
             const unsigned v = f[y * A.Wb + x];
             m &= v | (px_primal_empty(v) ? DSDF_PX_EMPTY : 0u);
             if (abs(y - py) <= 2 && abs(x - px) <= 2) near &= v;
+            if (p) {
+                const unsigned w = v | (p[y * A.Wb + x] & DSDF_PX_KEEP);
+                m3 &= w | (px_primal_empty(w) ? DSDF_PX_EMPTY : 0u);
+                if (abs(y - py) <= 2 && abs(x - px) <= 2) near3 &= w;
+            }
         }
-    f[i] = (unsigned char)((f[i] & DSDF_PX_KEEP) | ((m & 3u) << 2) | ((m & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near ? DSDF_PX_ONE : 0u));
+    const unsigned own = f[i];
+    f[i] = (unsigned char)((own & DSDF_PX_KEEP) | ((m & 3u) << 2) | ((m & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near ? DSDF_PX_ONE : 0u));
+    if (p) p[i] = (unsigned char)(((own | p[i]) & DSDF_PX_KEEP) | ((m3 & 3u) << 2) | ((m3 & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near3 ? DSDF_PX_ONE : 0u));
 }
 
 // sdf_direct_reparam with a VISIBLE environment (round 6): a sample that misses carries the environment's radiance, so "far" pixels
@@ -228,6 +274,15 @@ static BoundGrid max_bounds(const float *padded, int rx, int ry, int rz) {
     B.off = 0.f;
     B.b = c + hit_cells(rx, ry, rz);
     return B;
+}
+// The third stage's gradient bound D[0..2] (k_tap_diff_max): the first floats of the UNDILATED block maxima, which nothing reads once
+// k_coarse_dilate has produced the dilated ones (max_bounds, min_bounds and the kernels see only the dilated arrays; no test or host
+// harness looks inside the buffer) -- the grid buffer does not grow.  nullptr: a grid of fewer than three such blocks, no third stage.
+static float *grad_bound(const float *padded, int rx, int ry, int rz) {
+    if (hit_cells(rx, ry, rz) < 3) return nullptr;
+    const float *c = padded + padded_floats(rx, ry, rz);
+    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
+    return const_cast<float *>(c);
 }
 // [.. | block maxima, dilated | fine window maxima (rz,ry,rx) | fine window minima (rz,ry,rx)]
 static float *fine_buffer(const float *padded, int rx, int ry, int rz) {

@@ -17,6 +17,7 @@ DSDF_REPARAM = 1
 DSDF_NO_SKIP = 2
 DSDF_NO_HIT_PROOF = 4
 DSDF_NO_FINE_EMPTY = 8
+DSDF_NO_VALUE_BOUND = 16
 
 
 class DsdfCamera(C.Structure):

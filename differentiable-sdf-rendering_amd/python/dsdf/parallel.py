@@ -102,8 +102,16 @@ def row_costs(flags, n_views, Wb, Hb, spp, spp_grad, silhouette=True):
     (profiles/valu_model.json: a traced primal chunk ~ 24 wave iterations x 176 + 1454, a proven one ~ 500, a traced chunk of the
     sweep ~ 20 x 759): only their RATIOS matter."""
     import torch
-    f = flags[:n_views * Wb * Hb].view(n_views, Hb, Wb)
-    empty, empty_g, far, far_g, hit, deep = ((f & b) != 0 for b in (1, 2, 4, 8, 16, 32))
+    n = n_views * Wb * Hb
+    f = flags[:n].view(n_views, Hb, Wb)
+    if flags.numel() >= 2 * n:
+        # two planes (HipOps.begin_group): the render stages read the second, the library's effective plane with the third proof
+        # stage's results, when that stage ran -- it then holds a real flag byte in every pixel, never the 0xff begin_group left
+        # there (no byte carries "all miss" and "all hit" at once).  No host synchronisation: the choice is made on the device.
+        p = flags[n:2 * n].view(n_views, Hb, Wb)
+        f = torch.where(p[0, 0, 0] != 255, p, f)
+    # (bit 7: "every sample of the primal misses" as the finer proof stages report it, csrc/dsdf_proof.h: px_primal_empty)
+    empty, empty_g, far, far_g, hit, deep = ((f & b) != 0 for b in (1 | 128, 2, 4, 8, 16, 32))
     listed_p = ~far & ~(deep if silhouette else torch.zeros_like(deep))
     proven_p = listed_p & (empty | (hit if silhouette else torch.zeros_like(hit)))
     traced_p = listed_p & ~proven_p
@@ -347,9 +355,14 @@ class HipOps:
         self._group_i = gi + 1
         while len(bufs) <= gi:
             bufs.append(None)
-        if bufs[gi] is None or bufs[gi].numel() < n:
-            bufs[gi] = torch.empty(n, dtype=torch.uint8, device=dev)
+        # (two planes each: the flags row_costs reads, and behind them the library's effective plane of the third proof stage)
+        if bufs[gi] is None or bufs[gi].numel() < 2 * n:
+            bufs[gi] = torch.empty(2 * n, dtype=torch.uint8, device=dev)
         self._flags = bufs[gi]
+        # (row_costs: 0xff = "the effective plane was not written"; on the stream of the sweep, whose proof writes the planes next)
+        import contextlib
+        with (torch.cuda.stream(self._side) if (self._side is not None and self._in_sweeps) else contextlib.nullcontext()):
+            self._flags[n:2 * n].fill_(255)
         self._share_lib = self.r.share_proof_open(self.grid, self.kw.get('shading'), self._flags)
 
     def end_group(self):

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (DSDF_DIRECT, DSDF_NO_FINE_EMPTY, DSDF_NO_HIT_PROOF, DSDF_NO_SKIP, DSDF_REPARAM, DSDF_SILHOUETTE, DSDF_SIMPLE_SHADING, DsdfCamera,
+from ._lib import (DSDF_DIRECT, DSDF_NO_FINE_EMPTY, DSDF_NO_HIT_PROOF, DSDF_NO_VALUE_BOUND, DSDF_NO_SKIP, DSDF_REPARAM, DSDF_SILHOUETTE, DSDF_SIMPLE_SHADING, DsdfCamera,
                    DsdfShading)
 
 INTEGRATORS = {'sdf_silhouette_reparam': DSDF_SILHOUETTE, 'sdf_simple_shading_reparam': DSDF_SIMPLE_SHADING,
@@ -31,11 +31,14 @@ _workspaces = {}
 
 def _proof_flags(empty_space_skip):
     """True: both per-pixel proofs (csrc/dsdf_proof.h); 'empty-only': without the hit proof of the silhouette primal; 'coarse-empty':
-    without the second stage of the empty-space proof on the full-resolution window minima (A/B and tests); False: none."""
+    without the second stage of the empty-space proof on the full-resolution window minima, and the third with it; 'window-empty':
+    without the third stage only, the spline value on the centre ray -+ a gradient bound (both A/B and tests); False: none."""
     if empty_space_skip == 'empty-only':
         return DSDF_NO_HIT_PROOF
     if empty_space_skip == 'coarse-empty':
         return DSDF_NO_FINE_EMPTY
+    if empty_space_skip == 'window-empty':
+        return DSDF_NO_VALUE_BOUND
     return 0 if empty_space_skip else DSDF_NO_SKIP
 
 # Views traced by one kernel launch (bounded by the workspace: the backward queue of a GRADIENT pass holds 40 B per
@@ -723,7 +726,8 @@ def step_begin(grid, sensors, spp, spp_grad, seeds, seeds_grad, integrator=DSDF_
         side = _side_streams[dev] = torch.cuda.Stream(dev, priority=-1)
     side.wait_stream(main)                                    # the grid (and whatever produced it) is ready
     # one per-pixel proof for both passes (dsdf_share_pixel_skip): the sweep writes the flags, the primal render reads them
-    nflag = len(sensors) * (W + 4) * (H + 4)
+    # (two planes: the flags a caller may read, and behind them the library's effective plane of the third proof stage)
+    nflag = 2 * len(sensors) * (W + 4) * (H + 4)
     flags = _skip_buffers.get(dev)
     if flags is None or flags.numel() < nflag:
         flags = _skip_buffers[dev] = torch.empty(nflag, dtype=torch.uint8, device=dev)

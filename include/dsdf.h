@@ -51,8 +51,10 @@ enum dsdf_flags {
     DSDF_REPARAM = 1,
     DSDF_NO_SKIP = 2,        /* disable the exact per-pixel proofs (empty space and hit; A/B and testing) */
     DSDF_NO_HIT_PROOF = 4,   /* keep the empty-space proof, disable the hit proof of the silhouette primal (csrc/dsdf_proof.h) */
-    DSDF_NO_FINE_EMPTY = 8   /* keep the proofs on the block bounds, disable the second stage of the empty-space proof on the
-                                full-resolution window minima (A/B and testing) */
+    DSDF_NO_FINE_EMPTY = 8,  /* keep the proofs on the block bounds, disable the second stage of the empty-space proof on the
+                                full-resolution window minima -- and the third with it (A/B and testing) */
+    DSDF_NO_VALUE_BOUND = 16 /* keep both stages above, disable the third: spline value on the centre ray -+ a gradient bound
+                                (csrc/dsdf_proof.h: ValueBound; A/B and testing) */
 };
 
 /* Perspective sensor as built by python/util.py:115-138 (`get_regular_cameras`):
@@ -371,7 +373,10 @@ int dsdf_set_grid_transform(const float *to_local, const float *aabb_lo, const f
  * carries no boundary weight in the gradient pass (either stage); bits 2 / 3 the whole +-4 neighbourhood is proven empty for the
  * primal / the gradient pass; bit 4 every sample hits; bits 5 / 6 its dilations; bit 7 every sample of the primal misses, proven by
  * the second stage on the full-resolution window minima (never set together with a new bit 0: bit 0 keeps its meaning, a reader
- * that wants "the primal misses" tests bit 0 OR bit 7).  DSDF_NO_FINE_EMPTY leaves bit 7 clear. */
+ * that wants "the primal misses" tests bit 0 OR bit 7).  DSDF_NO_FINE_EMPTY leaves bit 7 clear.
+ * A buffer of at least TWO bytes per film-block pixel and view lets the third proof stage run inside the bracket: the first half is
+ * written exactly as described above, the second half is the library's own effective plane (what the render stages read: the same
+ * bits with the third stage's results added) and no part of the interface. */
 int dsdf_share_pixel_skip(void *buffer, size_t bytes);
 
 /* Measurement hook: after dsdf_kernel_timing_arm() the next render call of the calling thread (dsdf_render_forward /

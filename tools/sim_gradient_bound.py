@@ -1,0 +1,253 @@
+#!/usr/bin/env python3
+"""Offline study (CPU, test infrastructure: uses oracle/ and tests/harness), sibling of tools/sim_proofs.py: how much marching would
+a THIRD proof stage remove -- the exact spline value on the centre ray minus a gradient bound?
+
+Stage 2 bounds the field near a centre-ray point x by the minimum / maximum of a 6^3 tap window.  Every gradient component
+of a tricubic B-spline is a convex combination of differences of adjacent taps (cubic weights across, quadratic weights along the
+axis: all >= 0, sum 1), so for every y within r voxels of x
+
+    |v(y) - v(x)| <= r * |(D_x, D_y, D_z)|_2          (voxel units; D_a = largest |tap difference| along axis a the lookups can touch)
+
+with r = lateral deviation + half a step (< 1 voxel: hit_step_fine).  This replays, on bench views, the proofs with the bound
+max(window minimum, v(x) - r |D|) (empty) and min(window maximum, v(x) + r |D|) (hit) in the unchanged logic of pixel_empty_proof /
+pixel_hit_proof, for several representations of D: one global figure, per block of 8^3 / 4^3 voxels dilated by one block, and per cell
+(the exact 6^3 window: the best any representation can do).  It weighs the pixels each settles by the steps the fp32 C oracle needs for
+their sample rays and checks every newly proven pixel against those rays (0 violations or the bound is wrong).
+
+    python tools/sim_gradient_bound.py [views, comma-separated: default 0,4,8] [spp]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'oracle'), os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools'),
+          os.path.join(ROOT, 'differentiable-sdf-rendering_amd', 'python')):
+    sys.path.insert(0, p)
+import c_oracle
+import sdf_oracle as O
+import __graft_entry__ as g
+from bench import synth_grid
+from conftest import HostHarness
+
+PX_EMPTY, PX_EMPTY_G, PX_HIT = 1, 2, 16
+GROW = 0.02
+
+
+def window(grid, fn, lo, hi, axes=(0, 1, 2)):
+    """per cell c: fn over the entries [c + lo[ax], c + hi[ax]] per axis (clamped), separable"""
+    a = grid
+    for ax in axes:
+        n = a.shape[ax]
+        idx = np.arange(n)
+        out = None
+        for o in range(lo[ax], hi[ax] + 1):
+            t = np.take(a, np.clip(idx + o, 0, n - 1), axis=ax)
+            out = t if out is None else fn(out, t)
+        a = out
+    return a
+
+
+def tap_differences(grid):
+    """|grid[i + 1] - grid[i]| along z, y, x, stored at i (0 at the last entry: the clamped tap repeats)"""
+    out = []
+    for ax in range(3):
+        d = np.zeros_like(grid)
+        sl = [slice(None)] * 3
+        sl[ax] = slice(0, -1)
+        d[tuple(sl)] = np.abs(np.diff(grid, axis=ax))
+        out.append(d)
+    return out
+
+
+def gradient_bounds(grid):
+    """name -> (L, shift): L[cell >> shift] = |D|_2 over every tap difference the lookups within one voxel of a point of the cell touch
+    (taps [c - 2, c + 3]: differences stored at [c - 2, c + 2] along their own axis)."""
+    diffs = tap_differences(grid)
+    out = {}
+    out['global'] = (np.full((1, 1, 1), np.sqrt(sum(float(d.max()) ** 2 for d in diffs)), np.float32), 30)
+    for shift in (3, 2):
+        C = 1 << shift
+        D2 = 0
+        for d in diffs:
+            n = [(s + C - 1) // C for s in d.shape]
+            p = np.zeros([k * C for k in n], d.dtype)
+            p[:d.shape[0], :d.shape[1], :d.shape[2]] = d
+            b = p.reshape(n[0], C, n[1], C, n[2], C).max((1, 3, 5))
+            b = window(b, np.maximum, (-1, -1, -1), (1, 1, 1))            # (c - 2 .. c + 3 stay within one block of c's block)
+            D2 = D2 + b.astype(np.float64) ** 2
+        out[f'block{C}'] = (np.sqrt(D2).astype(np.float32), shift)
+    D2 = 0
+    for ax, d in enumerate(diffs):
+        lo, hi = [-2, -2, -2], [3, 3, 3]
+        hi[ax] = 2
+        D2 = D2 + window(d, np.maximum, lo, hi).astype(np.float64) ** 2
+    out['cell'] = (np.sqrt(D2).astype(np.float32), 0)
+    return out
+
+
+def main():
+    views = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else '0,4,8').split(',')]
+    spp = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    res = 256
+    grid = synth_grid(res, 'cpu').numpy()
+    t0 = time.time()
+    Fmin = window(grid, np.minimum, (-2, -2, -2), (3, 3, 3))
+    Fmax = window(grid, np.maximum, (-2, -2, -2), (3, 3, 3))
+    bounds = gradient_bounds(grid)
+    print(f'bounds: {time.time() - t0:.1f}s; |D|_2 in voxels of distance per voxel: ' +
+          ', '.join(f'{k} mean {L.mean() * res:.3f} max {L.max() * res:.3f}' for k, (L, s) in bounds.items()), flush=True)
+    for view in views:
+        print(f'==== view {view}, {spp} samples per pixel', flush=True)
+        replay(view, spp, grid, Fmin, Fmax, bounds)
+
+
+def replay(view, spp, grid, Fmin, Fmax, bounds):
+    res, W = grid.shape[0], 512
+    camo = O.Camera(O.regular_camera_origins(12)[view]).rounded()
+    cam = camo.params()
+    hh = HostHarness(g.build_harness())
+    prm = hh.params
+    lib = c_oracle.load(False)
+    flags, info = hh.pixel_proof(grid, cam, W, W)
+    empty, empty_g, hit = (flags & PX_EMPTY) != 0, (flags & PX_EMPTY_G) != 0, (flags & PX_HIT) != 0
+    fstep = float(info[3])
+    # lateral deviation (dsdf_proof.h: pixel_spread_voxels) + half a step
+    t_far = float(np.linalg.norm(camo.origin.numpy() - 0.5)) + 1.0
+    worst = t_far * 0.7072 * (2 * camo.tan / W) * res
+    r = worst + 0.5 * fstep * res
+    print(f'fine step {fstep * res:.3f} voxels, lateral deviation {worst:.3f}, r {r:.3f}')
+
+    # centre rays of every pixel the coarse stage leaves without bit 1 (the work list of the fine stages)
+    py, px = np.nonzero(~empty_g)
+    pos = np.stack([px - 2 + 0.5, py - 2 + 0.5], -1).astype(np.float64)
+    o, d, _ = camo.sample_ray(torch.from_numpy(pos), W, W)
+    o, d = o.numpy(), d.numpy()
+    d = d / np.linalg.norm(d, axis=1, keepdims=True)
+
+    def box(grow):
+        lo, hi = -prm.bbox_delta - grow, 1 + prm.bbox_delta + grow
+        with np.errstate(divide='ignore', invalid='ignore'):
+            ta, tb = (lo - o) / d, (hi - o) / d
+        tn, tf = np.minimum(ta, tb).max(1), np.maximum(ta, tb).min(1)
+        return tf >= np.maximum(tn, 0), np.maximum(tn, 0), tf
+
+    ok, tn, tf = box(GROW)
+    iok, i0, i1 = box(-GROW)
+    n = len(px)
+    nst = int(np.ceil((tf - tn)[ok].max() / fstep)) + 2
+    t1 = tf
+    thr_p = 2 * prm.trace_eps * np.maximum(t1, 1) + 1e-5
+    thr_g = np.maximum(thr_p, prm.edge_eps * (t1 + 0.1) * 1.05 + 1e-4)
+
+    # per sample position: window bounds, spline value where a window bound fails its threshold, cell
+    t0 = time.time()
+    T = np.minimum(tn[:, None] + np.arange(nst)[None, :] * fstep, tf[:, None])           # (n, nst)
+    live = (tn[:, None] + np.arange(nst)[None, :] * fstep < (t1 + fstep)[:, None]) & ok[:, None]
+    X = o[:, None, :] + T[:, :, None] * d[:, None, :]
+    c = np.clip(np.floor(X * res - 0.5).astype(np.int64), 0, res - 1)
+    lo_w = Fmin[c[..., 2], c[..., 1], c[..., 0]]
+    hi_w = Fmax[c[..., 2], c[..., 1], c[..., 0]]
+    want = live & ((lo_w <= thr_g[:, None]) | (hi_w >= 0))
+    V = np.zeros(T.shape, np.float32)
+    V[want] = c_oracle.eval_cubic(lib, grid, X[want])[0]
+    print(f'{n} listed pixels x {nst} positions, {want.sum()} spline values ({want.sum() / max(live.sum(), 1):.3f} of the positions): '
+          f'{time.time() - t0:.0f}s', flush=True)
+
+    def proofs(L, shift):
+        """(empty, empty_g, hit) of the listed pixels with the window bounds tightened by value -+ r L (L None: stage 2 alone)"""
+        if L is None:
+            lo_b, hi_b = lo_w, hi_w
+        else:
+            b = c >> shift
+            b = np.minimum(b, np.array(L.shape[::-1]) - 1)
+            m = r * L[b[..., 2], b[..., 1], b[..., 0]]
+            lo_b = np.where(want, np.maximum(lo_w, V - m), lo_w)
+            hi_b = np.where(want, np.minimum(hi_w, V + m), hi_w)
+        m = np.where(live, lo_b, np.inf).min(1)
+        e, eg = ok & (m > thr_p), ok & (m > thr_g)
+        # pixel_hit_proof, sample by sample
+        half = 0.5 * fstep
+        J = np.full(n, -np.inf); Jrun = np.zeros(n); in_run = np.zeros(n, bool); h = np.zeros(n, bool)
+        for k in range(nst):
+            tc, U, lv = T[:, k], hi_b[:, k], live[:, k]
+            neg = lv & (U < 0) & (tc - half >= i0) & (tc + half <= i1)
+            start = neg & ~in_run
+            Jrun = np.where(start, J, Jrun)
+            in_run = np.where(lv, neg, in_run)
+            h |= neg & (tc + half >= Jrun + 1e-4)
+            J = np.where(lv, np.maximum(J, tc + half + U), J)
+        h &= ok & iok & ~e
+        return e, eg, h
+
+    def full(e, eg, h):
+        E, EG, H = empty.copy(), empty_g.copy(), hit.copy()
+        E[py, px] |= e; EG[py, px] |= eg
+        H[py, px] |= h & ~E[py, px]
+        return E, EG, H
+
+    E2, EG2, H2 = full(*proofs(None, 0))
+    print(f'stage 2 (shipped): empty {E2.mean():.4f} empty_g {EG2.mean():.4f} hit {H2.mean():.4f} primal-traced {(~E2 & ~H2).mean():.4f} '
+          f'sweep-traced {(~EG2).mean():.4f}', flush=True)
+    stage3 = {}
+    for name, (L, shift) in bounds.items():
+        E3, EG3, H3 = full(*proofs(L, shift))
+        assert (E2 <= E3).all() and (EG2 <= EG3).all() and (H2 & ~E3 <= H3).all()
+        stage3[name] = (E3, EG3, H3)
+        print(f'stage 3 [{name}]: empty {E3.mean():.4f} empty_g {EG3.mean():.4f} hit {H3.mean():.4f} primal-traced {(~E3 & ~H3).mean():.4f} '
+              f'sweep-traced {(~EG3).mean():.4f}; newly proven hit {(H3 & ~H2).sum()} pixels', flush=True)
+
+    # steps of the sample rays of every pixel stage 2 leaves to the march
+    rng = np.random.default_rng(0)
+
+    def trace(mask, diff):
+        qy, qx = np.nonzero(mask)
+        steps = np.zeros((len(qx), spp), np.int32)
+        hits = np.zeros((len(qx), spp), bool)
+        need = np.zeros((len(qx), spp), bool)
+        B = 20000
+        for a in range(0, len(qx), B):
+            b = min(len(qx), a + B)
+            pos = np.stack([qx[a:b], qy[a:b]], -1).reshape(-1, 1, 2) - 2 + rng.random((b - a, spp, 2))
+            oo, dd, mt = camo.sample_ray(torch.from_numpy(pos.reshape(-1, 2)), W, W)
+            tr = c_oracle.trace(lib, grid, oo.numpy(), dd.numpy(), mt.numpy(), diff=diff)
+            steps[a:b] = tr['steps'].reshape(-1, spp)
+            hits[a:b] = np.isfinite(tr['its_t']).reshape(-1, spp)
+            if diff:
+                # the BOUNDARY weight (csrc/dsdf_math.h: warp_weight_positive), as tools/sim_proofs.py tests it
+                wt = tr['warp_t'].astype(np.float64)
+                fin = np.isfinite(wt) & (tr['warp_weight'] > 0)
+                x = oo.numpy()[fin] + wt[fin, None] * dd.numpy()[fin]
+                v = np.asarray(c_oracle.eval_cubic(lib, grid, x)[0], np.float64).reshape(-1)
+                bd = np.maximum(0.0, np.minimum((x + prm.bbox_delta).min(1), (1 + prm.bbox_delta - x).min(1)))
+                eps = np.minimum(prm.edge_eps * wt[fin] if prm.weight_strategy == 6 else prm.edge_eps, bd)
+                w = np.zeros(len(wt), bool)
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    w[fin] = 1.0 - np.abs(v) / eps > 0
+                need[a:b] = w.reshape(-1, spp)
+        return qy, qx, steps, hits, need
+
+    for pname, now, diff in (('primal', ~E2 & ~H2, False), ('sweep', ~EG2, True)):
+        t0 = time.time()
+        qy, qx, steps, hits, need = trace(now, diff)
+        lane, wave = steps.sum(), steps.max(1).sum()
+        print(f'{pname}: {len(qx)} pixels traced after stage 2, lane-steps {lane}, lock-step iterations (max over {spp} samples) {wave}   '
+              f'[{time.time() - t0:.0f}s]', flush=True)
+        for name, (E3, EG3, H3) in stage3.items():
+            keep = (~EG3 if diff else ~E3 & ~H3)[qy, qx]
+            drop = ~keep
+            lane2, wave2 = steps[keep].sum(), steps[keep].max(1).sum()
+            if diff:
+                bad = int((need[drop] | hits[drop]).any(1).sum())
+            else:
+                de, dh = drop & E3[qy, qx], drop & H3[qy, qx]
+                bad = int(hits[de].any(1).sum() + (~hits[dh]).any(1).sum())
+            print(f'   [{name}] traced pixels x {keep.mean():.3f}; lane-steps x {lane2 / lane:.3f}; lock-step iterations x {wave2 / wave:.3f}; '
+                  f'violations among {drop.sum()} newly proven pixels (must be 0): {bad}', flush=True)
+
+
+if __name__ == '__main__':
+    main()
