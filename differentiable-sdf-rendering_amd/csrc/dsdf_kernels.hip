@@ -78,7 +78,7 @@ __global__ void k_pad_grid(const float *__restrict__ data, int rx, int ry, int r
     }
 }
 
-// The row-block copy of the padded grid (dsdf_math.h: DSDF_TLAYOUT): T[xc][z][y][0..7] = padded[z][y][4 xc .. 4 xc + 7] (x clamped to
+// The row-block copy of the padded grid (dsdf_math.h: GridView): T[xc][z][y][0..7] = padded[z][y][4 xc .. 4 xc + 7] (x clamped to
 // the padded row: the taps beyond it are never part of a cell).  One thread per 16-byte half row.
 __global__ void k_tlayout(const float *__restrict__ padded, int sx, int sy, int sz, int nxc, float *__restrict__ out) {
     const size_t n = (size_t)nxc * sz * sy * 2;
@@ -1197,84 +1197,58 @@ void dsdf_default_params(dsdf_params *p) {
     p->light_dir[0] = p->light_dir[1] = p->light_dir[2] = 0.57735026918962576f;
 }
 
-size_t dsdf_padded_size(int rx, int ry, int rz) {
-    size_t n = padded_floats(rx, ry, rz);
-    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) n += 2 * coarse_cells(rx, ry, rz, l);
-    n += 2 * hit_cells(rx, ry, rz) + 2 * (size_t)rx * ry * rz;            // (+ fine window maxima and their scratch)
-#if DSDF_TLAYOUT
-    n = tlayout_offset(rx, ry, rz) + tlayout_floats(rx, ry, rz);          // (+ the row-block copy the device lookups read)
-#endif
-    return n;
-}
+size_t dsdf_padded_size(int rx, int ry, int rz) { return grid_layout(rx, ry, rz).total; }
 
 int dsdf_pad_grid(const float *data, int rx, int ry, int rz, float *padded, void *stream) {
     if (!data || !padded || rx < 1 || ry < 1 || rz < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_pad_grid: bad argument");
-#if DSDF_TLAYOUT
     if ((uint64_t)32 * (ry + 2 * DSDF_APRON) * (rz + 2 * DSDF_APRON) >= (1u << 24) || tlayout_floats(rx, ry, rz) * 4 >= ((uint64_t)1 << 32))
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_pad_grid: grid too large for the row-block copy (24-bit stride, 32-bit offsets: about 717^3)");
-#endif
-    size_t n = padded_floats(rx, ry, rz);
+    const GridLayout L = grid_layout(rx, ry, rz);
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n = L.min_raw[0] - L.padded;          // (the floats of the padded copy)
     int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-    hipLaunchKernelGGL(k_pad_grid, dim3(grid), dim3(256), 0, (hipStream_t)stream, data, rx, ry, rz, padded);
+    hipLaunchKernelGGL(k_pad_grid, dim3(grid), dim3(256), 0, st, data, rx, ry, rz, padded + L.padded);
     int rc = check_launch("k_pad_grid");
     if (rc) return rc;
     // conservative min-grids for the empty-space proof, max-grid for the hit proof
-    float *c0 = padded + n;
     for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) {
-        int cx, cy, cz;
-        coarse_dims(rx, ry, rz, l, cx, cy, cz);
-        int nc = cx * cy * cz;
-        float *c1 = c0 + nc;
-        hipLaunchKernelGGL(k_coarse_reduce<false>, dim3((nc + 63) / 64), dim3(64), 0, (hipStream_t)stream, data, rx, ry, rz, c0, cx, cy, cz,
-                           1 << DSDF_COARSE_SHIFT(l));
-        hipLaunchKernelGGL(k_coarse_dilate<false>, dim3((nc + 63) / 64), dim3(64), 0, (hipStream_t)stream, c0, c1, cx, cy, cz, 1);
-        c0 = c1 + nc;
+        const BlockDims d = block_dims(rx, ry, rz, DSDF_COARSE_SHIFT(l));
+        const dim3 g((unsigned)((d.cells + 63) / 64)), b(64);
+        hipLaunchKernelGGL(k_coarse_reduce<false>, g, b, 0, st, data, rx, ry, rz, padded + L.min_raw[l], d.cx, d.cy, d.cz, 1 << DSDF_COARSE_SHIFT(l));
+        hipLaunchKernelGGL(k_coarse_dilate<false>, g, b, 0, st, (const float *)padded + L.min_raw[l], padded + L.min_dil[l], d.cx, d.cy, d.cz, 1);
     }
     {
-        int cx, cy, cz;
-        hit_dims(rx, ry, rz, cx, cy, cz);
-        int nc = cx * cy * cz;
-        float *c1 = c0 + nc;
-        hipLaunchKernelGGL(k_coarse_reduce<true>, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, data, rx, ry, rz, c0, cx, cy, cz,
-                           1 << DSDF_HIT_SHIFT);
-        hipLaunchKernelGGL(k_coarse_dilate<true>, dim3((nc + 255) / 256), dim3(256), 0, (hipStream_t)stream, c0, c1, cx, cy, cz, DSDF_HIT_RADIUS);
+        const BlockDims d = block_dims(rx, ry, rz, DSDF_HIT_SHIFT);
+        const dim3 g((unsigned)((d.cells + 255) / 256)), b(256);
+        hipLaunchKernelGGL(k_coarse_reduce<true>, g, b, 0, st, data, rx, ry, rz, padded + L.max_raw, d.cx, d.cy, d.cz, 1 << DSDF_HIT_SHIFT);
+        hipLaunchKernelGGL(k_coarse_dilate<true>, g, b, 0, st, (const float *)padded + L.max_raw, padded + L.max_dil, d.cx, d.cy, d.cz, DSDF_HIT_RADIUS);
     }
-    if (float *D = grad_bound(padded, rx, ry, rz)) {
-        // the third proof stage's gradient bound, in the undilated block maxima the dilation above has just consumed (dsdf_skip.h)
-        if (hipMemsetAsync(D, 0, 3 * sizeof(float), (hipStream_t)stream) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(gradient bound) failed");
+    if (L.has_D) {
+        // the third proof stage's gradient bound, in the raw block maxima the dilation above has just consumed (GridLayout::D)
+        if (hipMemsetAsync(padded + L.D, 0, 3 * sizeof(float), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(gradient bound) failed");
         const unsigned g = (unsigned)((size_t)ry * rz < 4096 ? (size_t)ry * rz : 4096);
-        hipLaunchKernelGGL(k_tap_diff_max, dim3(g), dim3(256), 0, (hipStream_t)stream, data, rx, ry, rz, (int *)D);
+        hipLaunchKernelGGL(k_tap_diff_max, dim3(g), dim3(256), 0, st, data, rx, ry, rz, (int *)(padded + L.D));
     }
-    {   // fine window maxima F and minima S, three separable passes each (x, y, z)
-        float *F = fine_buffer(padded, rx, ry, rz), *S = F + (size_t)rx * ry * rz;
+    {   // window maxima F and minima S, three separable passes each (x, y, z), which ping-pong through the region T of the row-block
+        // copy, larger than the grid: k_tlayout fills it AFTER them
+        float *F = padded + L.win_max, *S = padded + L.win_min, *T = padded + L.rows;
         const size_t total = (size_t)rx * ry * rz;
         const dim3 g((unsigned)((total + 255) / 256)), b(256);
-        const hipStream_t st = (hipStream_t)stream;
-#if DSDF_TLAYOUT
-        // (the passes ping-pong through the region of the row-block copy, larger than the grid, which k_tlayout fills AFTER them:
-        // so the second full-resolution buffer, once their scratch, is free to hold the minima)
-        float *T = padded + tlayout_offset(rx, ry, rz);
         hipLaunchKernelGGL(k_window<false>, g, b, 0, st, data, S, total, rx, (size_t)1, DSDF_FINE_LO, DSDF_FINE_HI);
         hipLaunchKernelGGL(k_window<false>, g, b, 0, st, (const float *)S, T, total, ry, (size_t)rx, DSDF_FINE_LO, DSDF_FINE_HI);
         hipLaunchKernelGGL(k_window<false>, g, b, 0, st, (const float *)T, S, total, rz, (size_t)rx * ry, DSDF_FINE_LO, DSDF_FINE_HI);
-#else
-        float *T = S;
-#endif
         hipLaunchKernelGGL(k_window<true>, g, b, 0, st, data, F, total, rx, (size_t)1, DSDF_FINE_LO, DSDF_FINE_HI);
         hipLaunchKernelGGL(k_window<true>, g, b, 0, st, (const float *)F, T, total, ry, (size_t)rx, DSDF_FINE_LO, DSDF_FINE_HI);
         hipLaunchKernelGGL(k_window<true>, g, b, 0, st, (const float *)T, F, total, rz, (size_t)rx * ry, DSDF_FINE_LO, DSDF_FINE_HI);
     }
     if ((rc = check_launch("k_coarse_reduce/dilate/window"))) return rc;
-#if DSDF_TLAYOUT
     {   // the row-block copy, behind the window passes above, which use its region as their temporary
         const int sx = rx + 2 * DSDF_APRON, sy = ry + 2 * DSDF_APRON, sz = rz + 2 * DSDF_APRON, nxc = (int)tlayout_chunks(rx);
         const size_t nt = (size_t)nxc * sz * sy * 2;
         const int tg = (int)((nt + 255) / 256 < 16384 ? (nt + 255) / 256 : 16384);
-        hipLaunchKernelGGL(k_tlayout, dim3(tg), dim3(256), 0, (hipStream_t)stream, (const float *)padded, sx, sy, sz, nxc,
-                           padded + tlayout_offset(rx, ry, rz));
+        hipLaunchKernelGGL(k_tlayout, dim3(tg), dim3(256), 0, st, (const float *)padded + L.padded, sx, sy, sz, nxc, padded + L.rows);
         if ((rc = check_launch("k_tlayout"))) return rc;
     }
-#endif
     return DSDF_OK;
 }
 
@@ -1466,8 +1440,9 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     hipStream_t st = c.st;
     const size_t npix = c.Wb * c.Hb;
     skip = nullptr;
-    float step = 0.f;
-    const int level = (c.flags & DSDF_NO_SKIP) ? -1 : skip_level(cams, nv, c.W, c.rx, c.ry, c.rz, step);
+    if (c.flags & DSDF_NO_SKIP) return DSDF_OK;
+    const ProofMargins M = proof_margins(cams, nv, c.W, c.rx, c.ry, c.rz);
+    const int level = M.level;
     if (level < 0) return DSDF_OK;
     SkipShare &sh = t_share;
     const bool can_share = sh.buf && sh.ready && sh.bytes >= (size_t)nv * npix;
@@ -1478,10 +1453,10 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     }
     unsigned char *dst = (can_share && !sh.valid) ? sh.buf : ws.skip;       // (a second, different batch keeps its own flags)
     const bool want_hit = c.integrator == DSDF_SILHOUETTE && !(c.flags & DSDF_NO_HIT_PROOF) && c.spp >= HIT_PROOF_MIN_SPP;
-    const float hstep = want_hit ? hit_step(cams, nv, c.W, c.rx, c.ry, c.rz) : 0.f;
+    const float hstep = want_hit ? M.hstep : 0.f;
     // the second stage on the full-resolution bounds: the fine hit proof where the hit proof is wanted, the fine empty-space proof
-    // for every integrator (DSDF_NO_FINE_EMPTY, or a build without the window minima: off)
-    const float fstep = hit_step_fine(cams, nv, c.W, c.rx, c.ry, c.rz);
+    // for every integrator (DSDF_NO_FINE_EMPTY: off)
+    const float fstep = M.fstep;
     const BoundGrid none = {nullptr, 0, 0, 0, 0, 0.f};
     const BoundGrid fmin = (c.flags & DSDF_NO_FINE_EMPTY) ? none : fine_min_bounds(c.padded, c.rx, c.ry, c.rz);
     const bool fine = fstep > 0.f && (want_hit || fmin.b);
@@ -1492,18 +1467,17 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
     ValueBound vb = {nullptr, 0.f};
     if (fine && fmin.b && !(c.flags & DSDF_NO_VALUE_BOUND) && (dst != sh.buf || sh.bytes >= 2 * (size_t)nv * npix)) {
         vb.D = grad_bound(c.padded, c.rx, c.ry, c.rz);
-        vb.r = value_bound_reach(cams, nv, c.W, c.rx, c.ry, c.rz, fstep);
+        vb.r = M.reach;
     }
     unsigned char *plane = vb.D ? dst + (size_t)nv * npix : nullptr;
     // the pixels neither proof settles are listed in the (not yet built) work-list area of this workspace for the second
     // stage: [DSDF_MAX_GROUPS * DSDF_ITEM_HDR ..) holds one entry per film-block pixel and view
     uint32_t *und = fine ? ws.items + (size_t)DSDF_MAX_GROUPS * DSDF_ITEM_HDR - DSDF_UNDECIDED_HDR : nullptr;
     if (und && hipMemsetAsync(und, 0, sizeof(uint32_t), st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "hipMemsetAsync(undecided list) failed");
-    // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try)
-    const float step0 = level > 0 ? skip_step(cams, nv, c.W, c.rx, c.ry, c.rz, level - 1) : 0.f;
+    // (when the proof runs on the finer min-grid, the coarser one gets a first, cheaper try: M.step0)
     const dim3 pgrid((unsigned)((npix + 255) / 256), nv), blk(256);
     if ((rc = launch("k_pixel_skip", k_pixel_skip, pgrid, blk, st, device_view(c), min_bounds(c.padded, c.rx, c.ry, c.rz, level > 0 ? level - 1 : 0),
-                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, step0, step, hstep, und, list_g, plane)))
+                     min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, M.step0, M.step, hstep, und, list_g, plane)))
         return rc;
     if (und && (rc = launch("k_pixel_hit_fine", k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), blk, st, device_view(c),
                             fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), vb, c.pp, VB, dst, plane, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))

@@ -80,7 +80,7 @@ DSDF_HD V3 symmul(const float H[6], V3 a) {
 #define DSDF_APRON 3
 #define DSDF_COARSE_LEVELS 2   /* conservative min-grids over blocks of 8^3 (level 0) and 4^3 (level 1) voxels */
 #define DSDF_COARSE_SHIFT(level) (3 - (level))
-// Round 6: the ROW-BLOCK copy of the padded grid that the device lookups read (DSDF_TLAYOUT, on by default).  In the linear copy a
+// Round 6: the ROW-BLOCK copy of the padded grid that the device lookups read.  In the linear copy a
 // 128-byte line holds 32 x-consecutive taps of ONE (y, z) row, so the 16 rows (4 y x 4 z, four x-consecutive taps each) of a B-spline
 // cell sit in 16 different lines and a cell fill is 16 L2 requests for 16 useful bytes each -- the primal march made 2.8 G of them
 // per launch, 0.75 per clock and L2 channel: the request rate of the L2, not its capacity or HBM, bounded the fills.
@@ -90,10 +90,7 @@ DSDF_HD V3 symmul(const float H[6], V3 a) {
 // the linear copy (every tap twice).  Row (k, j) of the cell at byte offset `base` is at base + k * tz4 + j * 32: the same
 // "base + uniform offsets" form as the linear copy, so every row provider (per-lane gathers, the register-resident cell, the wave
 // cell cache, the 16-lane evaluator) is unchanged but for its two strides; only the cell address costs 4 more instructions.
-// The host build (tests/harness) and -DDSDF_TLAYOUT=0 read the linear copy.
-#ifndef DSDF_TLAYOUT
-#define DSDF_TLAYOUT 1
-#endif
+// The host build (tests/harness) reads the linear copy.
 struct GridView {
     const float *p;
     int rx, ry, rz;
@@ -286,7 +283,6 @@ DSDF_HD CubicCell cubic_cell_q(const GridView &G, V3 q) {
     asm("v_med3_i32 %0, %1, -2, %2" : "=v"(qx) : "v"(qx), "s"(G.rx));
     asm("v_med3_i32 %0, %1, -2, %2" : "=v"(qy) : "v"(qy), "s"(G.ry));
     asm("v_med3_i32 %0, %1, -2, %2" : "=v"(qz) : "v"(qz), "s"(G.rz));
-#if DSDF_TLAYOUT
     // row-block copy: base = (bx >> 2) * tx4 + bz * tz4 + by * 32 + (bx & 3) * 4 with b = q + 2 (the "+ 2" of y and z: one uniform constant)
     int bx, xo, lin;
     asm("v_add_u32 %0, 2, %1" : "=v"(bx) : "v"(qx));
@@ -299,14 +295,6 @@ DSDF_HD CubicCell cubic_cell_q(const GridView &G, V3 q) {
     const int c4 = 2 * (int)G.tz4 + 64;
     asm("v_add_u32 %0, %1, %2" : "=v"(cc.base) : "s"(c4), "v"(lin));
     return cc;
-#else
-    int lin;
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(lin) : "v"(qy), "s"(G.sx), "v"(qx));
-    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(lin) : "v"(qz), "s"(G.sxy), "v"(lin));
-    const int c4 = 8 * (G.sxy + G.sx + 1);
-    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(cc.base) : "v"(lin), "s"(c4));
-    return cc;
-#endif
 #else
     CubicSetup s = cubic_setup_q(G, q);
     int bx = iclamp(s.ix, -DSDF_APRON, G.rx - 1) + DSDF_APRON;
@@ -340,7 +328,7 @@ struct GlobalRows {
 };
 DSDF_HD GlobalRows global_rows(const GridView &G, const CubicCell &c) {
     GlobalRows r;
-#if defined(__HIP_DEVICE_COMPILE__) && DSDF_TLAYOUT
+#if defined(__HIP_DEVICE_COMPILE__)
     r.p = G.pt; r.base = c.base; r.sx4 = 32u; r.sxy4 = G.tz4;      // (row-block copy: y rows 32 bytes apart, z rows tz4)
 #else
     r.p = G.p; r.base = c.base; r.sx4 = 4u * (uint32_t)G.sx; r.sxy4 = 4u * (uint32_t)G.sxy;

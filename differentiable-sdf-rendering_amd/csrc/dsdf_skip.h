@@ -1,8 +1,10 @@
-// dsdf_skip.h -- exact empty-space proof (included by dsdf_kernels.hip): conservative min-grids of the SDF, the
-// per-pixel proof kernels and the host-side choice of the coarse level.
+// dsdf_skip.h -- the kernels of the per-pixel proofs (included by dsdf_kernels.hip): those that build the bounds behind the padded
+// grid, the proof kernels themselves, the dilation of their flags over the film, and the host-side views of the grid buffer
+// (GridLayout, dsdf_proof.h).  What a kernel computes per element is a statement of dsdf_proof.h, shared with the serial host builds
+// of the CPU tests: a kernel here decodes its index, calls it and stores.
 #pragma once
 
-// ------------------------------------------------------------------ per-pixel proofs (dsdf_proof.h)
+// ------------------------------------------------------------------ the bounds (dsdf_proof.h)
 // `c0[b]` = min (max) of the grid over coarse block b; `c[b]` = the same over the blocks within `radius` of b.  The
 // empty-space proof uses minima over 8^3 or 4^3 voxels dilated by one block (the finest level whose margin covers the pixel
 // footprint); the hit proof maxima over 2^3 voxels dilated by two blocks (a 10^3-voxel window: tighter, so that thin parts of
@@ -12,47 +14,20 @@ __global__ void k_coarse_reduce(const float *__restrict__ data, int rx, int ry, 
                                 int C) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cx * cy * cz) return;
-    int bx = i % cx, by = (i / cx) % cy, bz = i / (cx * cy);
-    float m = MAX ? -INFINITY : INFINITY;
-    for (int z = bz * C; z < min(rz, (bz + 1) * C); ++z)
-        for (int y = by * C; y < min(ry, (by + 1) * C); ++y)
-            for (int x = bx * C; x < min(rx, (bx + 1) * C); ++x) {
-                const float v = data[((size_t)z * ry + y) * rx + x];
-                m = MAX ? fmaxf(m, v) : fminf(m, v);
-            }
-    c0[i] = m;
+    c0[i] = block_reduce<MAX>(data, rx, ry, rz, i % cx, (i / cx) % cy, i / (cx * cy), C);
 }
 
 template <bool MAX>
 __global__ void k_coarse_dilate(const float *__restrict__ c0, float *__restrict__ c, int cx, int cy, int cz, int radius) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cx * cy * cz) return;
-    int bx = i % cx, by = (i / cx) % cy, bz = i / (cx * cy);
-    float m = MAX ? -INFINITY : INFINITY;
-    for (int z = max(bz - radius, 0); z <= min(bz + radius, cz - 1); ++z)
-        for (int y = max(by - radius, 0); y <= min(by + radius, cy - 1); ++y)
-            for (int x = max(bx - radius, 0); x <= min(bx + radius, cx - 1); ++x) {
-                const float v = c0[((size_t)z * cy + y) * cx + x];
-                m = MAX ? fmaxf(m, v) : fminf(m, v);
-            }
-    c[i] = m;
+    c[i] = block_dilate<MAX>(c0, cx, cy, cz, i % cx, (i / cx) % cy, i / (cx * cy), radius);
 }
 
-// Sliding-window maximum / minimum along one axis (stride `st` elements, extent n): out[i] = max(in[clamp(i + lo .. i + hi)]).  Three
-// passes (x, y, z) build the fine bounds of the hit proof (maxima) and of the empty-space proof (minima) from sdf.data
-// (dsdf_proof.h: hit_step_fine).
 template <bool MAX>
 __global__ void k_window(const float *__restrict__ in, float *__restrict__ out, size_t total, int n, size_t st, int lo, int hi) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int a = (int)((i / st) % (size_t)n);
-    float m = MAX ? -INFINITY : INFINITY;
-    for (int o = lo; o <= hi; ++o) {
-        const int b = min(max(a + o, 0), n - 1);
-        const float v = in[i + (size_t)(b - a) * st];   // (b - a may be negative: size_t wrap-around adds up correctly)
-        m = MAX ? fmaxf(m, v) : fminf(m, v);
-    }
-    out[i] = m;
+    if (i < total) out[i] = window_pass<MAX>(in, i, n, st, lo, hi);
 }
 
 // The gradient bound of the third proof stage (dsdf_proof.h: ValueBound): D[a] = the largest |difference of adjacent taps| along x, y, z
@@ -63,12 +38,8 @@ __global__ __launch_bounds__(256) void k_tap_diff_max(const float *__restrict__ 
     for (int row = blockIdx.x; row < ry * rz; row += gridDim.x) {
         const int y = row % ry, z = row / ry;
         const float *r = data + (size_t)row * rx;
-        for (int x = threadIdx.x; x < rx; x += blockDim.x) {
-            const float v = r[x];
-            if (x + 1 < rx) mx = fmaxf(mx, fabsf(r[x + 1] - v));
-            if (y + 1 < ry) my = fmaxf(my, fabsf(r[x + (size_t)rx] - v));
-            if (z + 1 < rz) mz = fmaxf(mz, fabsf(r[x + (size_t)rx * ry] - v));
-        }
+        for (int x = threadIdx.x; x < rx; x += blockDim.x)
+            tap_diff_fold(r + x, x + 1 < rx, y + 1 < ry, z + 1 < rz, (size_t)rx, (size_t)rx * ry, mx, my, mz);
     }
     // (thousands of atomics on three addresses would cost more than the pass over the grid: one wave per block reduces the block's
     // maxima and issues an atomic only for a value above what is stored -- D only grows)
@@ -100,12 +71,11 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
     unsigned f = DSDF_PX_EMPTY;
     if (valid) {
         int py = i / A.Wb, px = i - py * A.Wb;
-        CamRay r = camera_ray(A.cam, P, (float)(px - DSDF_BORDER) + 0.5f, (float)(py - DSDF_BORDER) + 0.5f, A.W, A.H);
-        V3 d = r.d * rsqf(dot(r.d, r.d));
-        if (step0 > 0.f) f = pixel_empty_proof(G, Bmin0, P, r.o, d, step0);
+        const CamRay r = pixel_centre_ray(A.cam, P, px, py, A.W, A.H);
+        if (step0 > 0.f) f = pixel_empty_proof(G, Bmin0, P, r.o, r.d, step0);
         else f = 0u;
-        if (f != (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G) && step > 0.f) f |= pixel_empty_proof(G, Bmin, P, r.o, d, step);
-        if (hstep > 0.f && !(f & DSDF_PX_EMPTY)) f |= pixel_hit_proof(G, Bmax, P, r.o, d, hstep);
+        if (f != (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G) && step > 0.f) f |= pixel_empty_proof(G, Bmin, P, r.o, r.d, step);
+        if (hstep > 0.f && !(f & DSDF_PX_EMPTY)) f |= pixel_hit_proof(G, Bmax, P, r.o, r.d, hstep);
         flags[(size_t)blockIdx.y * npix + i] = (unsigned char)f;
         if (plane) plane[(size_t)blockIdx.y * npix + i] = 0;         // (k_pixel_hit_fine adds what the third stage proves)
     }
@@ -123,7 +93,7 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
 }
 
 // Second stage of both proofs on the pixels k_pixel_skip listed.  First the empty-space proof, pixel_empty_proof itself over the
-// full-resolution window MINIMA (Bmin.b != nullptr): the block minima only prove a pixel whose rays stay 6-8 voxels clear of the
+// full-resolution window MINIMA (Bmin.b != nullptr: DSDF_NO_FINE_EMPTY switches the stage off): the block minima only prove a pixel whose rays stay 6-8 voxels clear of the
 // surface, these one whose rays stay about 3.  Its result goes to bit 7 (DSDF_PX_EMPTY_FINE) and bit 1, never to bit 0, which
 // keeps meaning "proven by the block minima".  Then, where that fails and the hit proof is wanted (hit), on the pixels without
 // bit 0, pixel_hit_proof (dsdf_proof.h) over the window maxima -- ~600 samples half a voxel apart per ray.  Inside k_pixel_skip that loop cost 1.2 ms per
@@ -144,16 +114,13 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bm
     const uint32_t e = list[i], npix = (uint32_t)(VB.v[0].Wb * VB.v[0].Hb), view = e / npix, pix = e - view * npix;
     const ViewArgs &A = VB.v[view];
     const int py = (int)(pix / (uint32_t)A.Wb), px = (int)(pix - (uint32_t)py * (uint32_t)A.Wb);
-    const CamRay r = camera_ray(A.cam, P, (float)(px - DSDF_BORDER) + 0.5f, (float)(py - DSDF_BORDER) + 0.5f, A.W, A.H);
-    const V3 d = r.d * rsqf(dot(r.d, r.d));
+    const CamRay r = pixel_centre_ray(A.cam, P, px, py, A.W, A.H);
     const unsigned f = flags[e];
     // both stages, both proofs, one loop over the sample positions (dsdf_proof.h); the hit proof only for the pixels without bit 0
-    const unsigned m = pixel_fine_proofs(G, Bmin, B, vb, P, r.o, d, step, hit && !(f & DSDF_PX_EMPTY));
-    const unsigned m2 = m & 0xffu, m3 = m >> 8;
-    const unsigned add = ((m2 & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m2 & (DSDF_PX_EMPTY_G | DSDF_PX_HIT));
+    const unsigned m = pixel_fine_proofs(G, Bmin, B, vb, P, r.o, r.d, step, hit && !(f & DSDF_PX_EMPTY));
+    const unsigned add = px_fine_bits(m & 0xffu), add3 = px_fine_bits(m >> 8);
     if (add) flags[e] = (unsigned char)(f | add);
     // the third stage's results never reach the caller-visible byte: the render stages read them from the effective plane
-    const unsigned add3 = ((m3 & DSDF_PX_EMPTY) ? DSDF_PX_EMPTY_FINE : 0u) | (m3 & (DSDF_PX_EMPTY_G | DSDF_PX_HIT));
     if (plane && add3) plane[e] = (unsigned char)add3;
 }
 
@@ -171,6 +138,17 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bm
 // `plane` (optional, the third stage's effective plane): holds the KEEP bits the third stage ADDS (k_pixel_hit_fine); this pass completes
 // it to what the render stages read -- the KEEP bits of flags | plane and bits 2 / 3 / 5 / 6 recomputed from those -- in the same
 // sweep over the neighbourhood.  In place like `flags`: a neighbour already rewritten holds flags' KEEP bits too, the same union.
+struct FarAcc {       // AND of bits 0 / 1 / 4 over the pixels within +-4 (bit 0: proven empty by either stage), of bit 4 over those within +-2
+    unsigned m = 3u | DSDF_PX_HIT, near = DSDF_PX_HIT;
+    __device__ void add(unsigned v, bool close) {
+        m &= v | (px_primal_empty(v) ? DSDF_PX_EMPTY : 0u);
+        if (close) near &= v;
+    }
+    // the stored byte: the pixel's own KEEP bits, bits 2 / 3 / 5 / 6 from the neighbourhood
+    __device__ unsigned char byte(unsigned own) const {
+        return (unsigned char)((own & DSDF_PX_KEEP) | ((m & 3u) << 2) | ((m & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near ? DSDF_PX_ONE : 0u));
+    }
+};
 __global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags, unsigned char *__restrict__ plane) {
     const ViewArgs &A = VB.v[blockIdx.y];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -178,21 +156,17 @@ __global__ void k_skip_dilate(ViewBatch VB, unsigned char *__restrict__ flags, u
     unsigned char *f = flags + (size_t)blockIdx.y * A.Wb * A.Hb;
     unsigned char *p = plane ? plane + (size_t)blockIdx.y * A.Wb * A.Hb : nullptr;
     int py = i / A.Wb, px = i - py * A.Wb;
-    unsigned m = 3u | DSDF_PX_HIT, near = DSDF_PX_HIT, m3 = m, near3 = near;
+    FarAcc af, ap;          // of the flag byte, of flags | plane
     for (int y = max(py - DSDF_FAR_RADIUS, 0); y <= min(py + DSDF_FAR_RADIUS, A.Hb - 1); ++y)
         for (int x = max(px - DSDF_FAR_RADIUS, 0); x <= min(px + DSDF_FAR_RADIUS, A.Wb - 1); ++x) {
             const unsigned v = f[y * A.Wb + x];
-            m &= v | (px_primal_empty(v) ? DSDF_PX_EMPTY : 0u);
-            if (abs(y - py) <= 2 && abs(x - px) <= 2) near &= v;
-            if (p) {
-                const unsigned w = v | (p[y * A.Wb + x] & DSDF_PX_KEEP);
-                m3 &= w | (px_primal_empty(w) ? DSDF_PX_EMPTY : 0u);
-                if (abs(y - py) <= 2 && abs(x - px) <= 2) near3 &= w;
-            }
+            const bool close = abs(y - py) <= 2 && abs(x - px) <= 2;
+            af.add(v, close);
+            if (p) ap.add(v | (p[y * A.Wb + x] & DSDF_PX_KEEP), close);
         }
     const unsigned own = f[i];
-    f[i] = (unsigned char)((own & DSDF_PX_KEEP) | ((m & 3u) << 2) | ((m & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near ? DSDF_PX_ONE : 0u));
-    if (p) p[i] = (unsigned char)(((own | p[i]) & DSDF_PX_KEEP) | ((m3 & 3u) << 2) | ((m3 & DSDF_PX_HIT) ? DSDF_PX_DEEP : 0u) | (near3 ? DSDF_PX_ONE : 0u));
+    f[i] = af.byte(own);
+    if (p) p[i] = ap.byte(own | p[i]);
 }
 
 // sdf_direct_reparam with a VISIBLE environment (round 6): a sample that misses carries the environment's radiance, so "far" pixels
@@ -238,78 +212,27 @@ __global__ void k_film_ones(ViewBatch VB, const unsigned char *__restrict__ flag
     }
 }
 
-// ---- host side: layout of the coarse levels behind the padded grid, level selection
-static size_t padded_floats(int rx, int ry, int rz) {
-    return (size_t)(rx + 2 * DSDF_APRON) * (ry + 2 * DSDF_APRON) * (rz + 2 * DSDF_APRON);
-}
-
-// The library's grid buffer: [padded grid | per level: block minima, dilated block minima | block maxima, dilated block maxima]
-//                             [.. | fine window maxima, fine window minima | row-block copy of the padded grid (dsdf_math.h: DSDF_TLAYOUT)]
-// (the minima live in what used to be the scratch of the maxima's passes; both sets of passes now ping-pong through the region of
-// the row-block copy BEFORE k_tlayout fills it -- a -DDSDF_TLAYOUT=0 build has no such region, keeps the scratch and has no minima)
-static size_t tlayout_offset(int rx, int ry, int rz);
+// ---- host side: views of the grid buffer (GridLayout, dsdf_proof.h)
 static GridView device_view(const float *padded, int rx, int ry, int rz, const dsdf_params &prm) {
     GridView G = make_view(padded, rx, ry, rz, prm);
-#if DSDF_TLAYOUT
-    G.pt = padded + tlayout_offset(rx, ry, rz);
-#endif
+    G.pt = padded + grid_layout(rx, ry, rz).rows;
     return G;
 }
+// the dilated block minima of one coarse level, the dilated block maxima, the window maxima, the window minima
 static BoundGrid min_bounds(const float *padded, int rx, int ry, int rz, int level) {
-    const float *c = padded + padded_floats(rx, ry, rz);
-    for (int l = 0; l < level; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
-    BoundGrid B;
-    coarse_dims(rx, ry, rz, level, B.cx, B.cy, B.cz);
-    B.shift = DSDF_COARSE_SHIFT(level);
-    B.off = 0.f;
-    B.b = c + coarse_cells(rx, ry, rz, level);
-    return B;
+    return bound_grid(padded + grid_layout(rx, ry, rz).min_dil[level], block_dims(rx, ry, rz, DSDF_COARSE_SHIFT(level)), DSDF_COARSE_SHIFT(level), 0.f);
 }
 static BoundGrid max_bounds(const float *padded, int rx, int ry, int rz) {
-    const float *c = padded + padded_floats(rx, ry, rz);
-    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
-    BoundGrid B;
-    hit_dims(rx, ry, rz, B.cx, B.cy, B.cz);
-    B.shift = DSDF_HIT_SHIFT;
-    B.off = 0.f;
-    B.b = c + hit_cells(rx, ry, rz);
-    return B;
-}
-// The third stage's gradient bound D[0..2] (k_tap_diff_max): the first floats of the UNDILATED block maxima, which nothing reads once
-// k_coarse_dilate has produced the dilated ones (max_bounds, min_bounds and the kernels see only the dilated arrays; no test or host
-// harness looks inside the buffer) -- the grid buffer does not grow.  nullptr: a grid of fewer than three such blocks, no third stage.
-static float *grad_bound(const float *padded, int rx, int ry, int rz) {
-    if (hit_cells(rx, ry, rz) < 3) return nullptr;
-    const float *c = padded + padded_floats(rx, ry, rz);
-    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
-    return const_cast<float *>(c);
-}
-// [.. | block maxima, dilated | fine window maxima (rz,ry,rx) | fine window minima (rz,ry,rx)]
-static float *fine_buffer(const float *padded, int rx, int ry, int rz) {
-    const float *c = padded + padded_floats(rx, ry, rz);
-    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) c += 2 * coarse_cells(rx, ry, rz, l);
-    return const_cast<float *>(c) + 2 * hit_cells(rx, ry, rz);
-}
-static size_t tlayout_offset(int rx, int ry, int rz) {
-    // (16-byte aligned like the padded grid itself: the rows are read with 4-byte-aligned 16-byte loads, the copy kernel writes float4)
-    size_t n = padded_floats(rx, ry, rz);
-    for (int l = 0; l < DSDF_COARSE_LEVELS; ++l) n += 2 * coarse_cells(rx, ry, rz, l);
-    n += 2 * hit_cells(rx, ry, rz) + 2 * (size_t)rx * ry * rz;
-    return (n + 3) & ~(size_t)3;
+    return bound_grid(padded + grid_layout(rx, ry, rz).max_dil, block_dims(rx, ry, rz, DSDF_HIT_SHIFT), DSDF_HIT_SHIFT, 0.f);
 }
 static BoundGrid fine_bounds(const float *padded, int rx, int ry, int rz) {
-    BoundGrid B;
-    B.cx = rx; B.cy = ry; B.cz = rz; B.shift = 0; B.off = 0.5f;
-    B.b = fine_buffer(padded, rx, ry, rz);
-    return B;
+    return bound_grid(padded + grid_layout(rx, ry, rz).win_max, block_dims(rx, ry, rz, 0), 0, 0.5f);
 }
-// The fine minima of the empty-space proof's second stage (b = nullptr: this build has none, the stage is off).
 static BoundGrid fine_min_bounds(const float *padded, int rx, int ry, int rz) {
-    BoundGrid B = fine_bounds(padded, rx, ry, rz);
-#if DSDF_TLAYOUT
-    B.b += (size_t)rx * ry * rz;
-#else
-    B.b = nullptr;
-#endif
-    return B;
+    return bound_grid(padded + grid_layout(rx, ry, rz).win_min, block_dims(rx, ry, rz, 0), 0, 0.5f);
+}
+// The third stage's gradient bound D[0..2] (k_tap_diff_max), nullptr: the grid has none, no third stage.
+static float *grad_bound(const float *padded, int rx, int ry, int rz) {
+    const GridLayout L = grid_layout(rx, ry, rz);
+    return L.has_D ? const_cast<float *>(padded) + L.D : nullptr;
 }

@@ -125,20 +125,33 @@ int         dsdf_version(void);
 const char *dsdf_last_error(void);
 void        dsdf_default_params(dsdf_params *p);
 
-/* Number of floats of the library's internal grid buffer for an (rz,ry,rx) grid:
- * the padded copy (clamp-to-edge apron of 3 voxels per side, so the 4^3 B-spline
- * footprint is always four contiguous 16-byte rows) followed by the bounds of the exact
- * per-pixel proofs (csrc/dsdf_proof.h): two coarse min-grids (8^3- and 4^3-voxel block minima
- * and their 3x3x3 dilations: pixels whose samples all MISS), a max-grid (2^3-voxel block maxima
- * and their 5x5x5 dilation: pixels whose samples all HIT; silhouette integrator) and two full-resolution
- * buffers, the window maxima (second stage of the hit proof) and the window minima (second stage of the
- * empty-space proof, every integrator).  The minima occupy what used to be the scratch of the maxima's
- * passes: dsdf_pad_grid now runs both sets of passes through the region of the row-block copy before it
- * fills that region, so the size is unchanged.  2.2 x the grid + 5 %: 213 MiB at 256^3. */
+/* Number of floats of the library's grid buffer for an (rz,ry,rx) grid: the padded copy followed by the bounds of the exact
+ * per-pixel proofs (csrc/dsdf_proof.h) and by the copy of the padded grid that the device lookups read.  In this order, with
+ * b(s) = ceil(rx / 2^s) * ceil(ry / 2^s) * ceil(rz / 2^s) (csrc/dsdf_proof.h: GridLayout holds the same table as offsets):
+ *
+ *   floats                              array, every one (z,y,x) with x fastest
+ *   (rx + 6)(ry + 6)(rz + 6)            padded copy: clamp-to-edge apron of 3 voxels per side, so the 4^3 B-spline footprint is
+ *                                       always four contiguous 16-byte rows
+ *   b(3), b(3)                          minima over blocks of 8^3 voxels: raw (scratch), dilated by one block (3x3x3)
+ *   b(2), b(2)                          minima over blocks of 4^3 voxels: raw (scratch), dilated by one block
+ *                                       -- pixels whose samples all MISS
+ *   b(1), b(1)                          maxima over blocks of 2^3 voxels: raw (scratch), dilated by two blocks (5x5x5)
+ *                                       -- pixels whose samples all HIT (silhouette integrator).  Where b(1) >= 3 the first three
+ *                                       floats of the raw array hold D, the largest |difference of adjacent voxels| along x, y, z
+ *                                       (third proof stage)
+ *   rx ry rz                            window maxima: per voxel c the maximum over the voxels [c - 2, c + 3]^3, clamped
+ *   rx ry rz                            window minima: the same with the minimum (second stage of both proofs)
+ *   (to a multiple of 4 floats)
+ *   ((rx + 2) / 4 + 1)(rz + 6)(ry + 6) 8   row-block copy T[xc][z][y][0..7] = padded[z][y][min(4 xc + k, rx + 5)]
+ *
+ * 2.2 x the grid + 5 % before the row-block copy, which is twice the padded copy: 213 MiB at 256^3.  The row-block copy is addressed
+ * with a 24-bit stride and 32-bit byte offsets: 32 (ry + 6)(rz + 6) < 2^24 and fewer than 2^30 floats, about 717^3.  This function
+ * returns the size whatever the grid; dsdf_pad_grid refuses a grid beyond the limit. */
 size_t dsdf_padded_size(int rx, int ry, int rz);
 
-/* Builds the padded copy.  Replaces `Texture3f.set_tensor` / `Grid3d.update`
- * (python/shapes.py:388, 473-479): call whenever `sdf.data` changes. */
+/* Builds the whole grid buffer -- the padded copy, the bounds and the row-block copy of the table above -- into `padded`
+ * (dsdf_padded_size floats, 16-byte aligned).  Replaces `Texture3f.set_tensor` / `Grid3d.update` (python/shapes.py:388, 473-479):
+ * call whenever `sdf.data` changes.  DSDF_ERR_INVALID_ARG for a grid beyond the limit of the row-block copy (about 717^3). */
 int dsdf_pad_grid(const float *data, int rx, int ry, int rz, float *padded, void *stream);
 
 /* A1: `Grid3d.eval / eval_and_grad / eval_all` (python/shapes.py:420-450), i.e.
@@ -250,7 +263,8 @@ int dsdf_render_backward(const float *padded, int rx, int ry, int rz, const dsdf
 
 /* `ReparamIntegrator.render_forward` (python/integrators/reparam.py:192-196): forward-mode gradient image
  * d image / d theta (n_views x H x W x 3) of a gradient-pass render at `spp`, for the tangent
- *   tangent_padded : d(sdf.data)/d theta as a padded grid buffer (dsdf_pad_grid of the tangent tensor), or NULL
+ *   tangent_padded : d(sdf.data)/d theta as a FULL grid buffer -- dsdf_pad_grid of the tangent tensor, dsdf_padded_size floats: the
+ *                    device lookups read its row-block copy, at the same offset as in `padded` -- or NULL
  *   tangent_p      : d(sdf.p)/d theta, 3 HOST floats, or NULL -- the reference's gradient-image validation
  *                    differentiates with respect to one axis of sdf.p (figures/result_utils.py:126-161).
  * All three integrators (sdf_direct_reparam: the albedo volume carries no tangent).  image_out (optional) receives the

@@ -46,6 +46,30 @@ static std::vector<float> pad(const float *data, int rx, int ry, int rz) {
     return out;
 }
 
+// Block bounds as k_coarse_reduce / k_coarse_dilate build them (dsdf_proof.h: block_reduce, block_dilate): min or max over blocks
+// of (1 << shift)^3 voxels, then over the blocks within `radius`.
+template <bool MAX>
+static std::vector<float> block_bounds(const float *data, int rx, int ry, int rz, int shift, int radius, BoundGrid &B) {
+    const BlockDims d = block_dims(rx, ry, rz, shift);
+    std::vector<float> c0(d.cells), c(d.cells);
+    for (size_t i = 0; i < d.cells; ++i)
+        c0[i] = block_reduce<MAX>(data, rx, ry, rz, (int)(i % d.cx), (int)(i / d.cx % d.cy), (int)(i / d.cx / d.cy), 1 << shift);
+    for (size_t i = 0; i < d.cells; ++i)
+        c[i] = block_dilate<MAX>(c0.data(), d.cx, d.cy, d.cz, (int)(i % d.cx), (int)(i / d.cx % d.cy), (int)(i / d.cx / d.cy), radius);
+    B = bound_grid(nullptr, d, shift, 0.f);       // (the caller points it at the vector it keeps)
+    return c;
+}
+
+// Window maxima as the three k_window passes build them (dsdf_proof.h: window_pass): along x, then y, then z.
+static std::vector<float> window_max(const float *data, int rx, int ry, int rz) {
+    const size_t total = (size_t)rx * ry * rz, st[3] = {1, (size_t)rx, (size_t)rx * ry};
+    const int n[3] = {rx, ry, rz};
+    std::vector<float> a(data, data + total), b(total);
+    for (int ax = 0; ax < 3; ++ax, a.swap(b))
+        for (size_t i = 0; i < total; ++i) b[i] = window_pass<true>(a.data(), i, n[ax], st[ax], DSDF_FINE_LO, DSDF_FINE_HI);
+    return a;
+}
+
 extern "C" {
 
 void hh_eval_cubic(const float *data, int rx, int ry, int rz, const dsdf_params *prm, const float *pts, long n,
@@ -484,90 +508,35 @@ void hh_sampler_bsdf(unsigned seed, long n, float *out) {
     for (long i = 0; i < n; ++i) sampler_bsdf_2d(seed, (uint32_t)i, out[2 * i], out[2 * i + 1]);
 }
 
-// Block bounds as k_coarse_reduce / k_coarse_dilate build them (dsdf_skip.h): min or max over blocks of C^3 voxels, then over
-// the blocks within `radius`.
-static std::vector<float> block_bounds(const float *data, int rx, int ry, int rz, int C, int radius, bool mx, int &cx, int &cy, int &cz) {
-    cx = (rx + C - 1) / C; cy = (ry + C - 1) / C; cz = (rz + C - 1) / C;
-    std::vector<float> c0((size_t)cx * cy * cz), c((size_t)cx * cy * cz);
-    for (int bz = 0; bz < cz; ++bz)
-        for (int by = 0; by < cy; ++by)
-            for (int bx = 0; bx < cx; ++bx) {
-                float m = mx ? -INFINITY : INFINITY;
-                for (int z = bz * C; z < std::min(rz, (bz + 1) * C); ++z)
-                    for (int y = by * C; y < std::min(ry, (by + 1) * C); ++y)
-                        for (int x = bx * C; x < std::min(rx, (bx + 1) * C); ++x) {
-                            float v = data[((size_t)z * ry + y) * rx + x];
-                            m = mx ? fmaxf(m, v) : fminf(m, v);
-                        }
-                c0[((size_t)bz * cy + by) * cx + bx] = m;
-            }
-    for (int bz = 0; bz < cz; ++bz)
-        for (int by = 0; by < cy; ++by)
-            for (int bx = 0; bx < cx; ++bx) {
-                float m = mx ? -INFINITY : INFINITY;
-                for (int z = std::max(bz - radius, 0); z <= std::min(bz + radius, cz - 1); ++z)
-                    for (int y = std::max(by - radius, 0); y <= std::min(by + radius, cy - 1); ++y)
-                        for (int x = std::max(bx - radius, 0); x <= std::min(bx + radius, cx - 1); ++x) {
-                            float v = c0[((size_t)z * cy + y) * cx + x];
-                            m = mx ? fmaxf(m, v) : fminf(m, v);
-                        }
-                c[((size_t)bz * cy + by) * cx + bx] = m;
-            }
-    return c;
-}
-
-// Sliding-window maxima as k_window_max builds them (dsdf_skip.h): max over [i + lo, i + hi] (clamped) along x, then y, then z.
-static std::vector<float> window_max(const float *data, int rx, int ry, int rz, int lo, int hi) {
-    const size_t total = (size_t)rx * ry * rz;
-    std::vector<float> a(data, data + total), b(total);
-    const int n[3] = {rx, ry, rz};
-    const size_t st[3] = {1, (size_t)rx, (size_t)rx * ry};
-    for (int ax = 0; ax < 3; ++ax) {
-        for (size_t i = 0; i < total; ++i) {
-            const int c = (int)((i / st[ax]) % (size_t)n[ax]);
-            float m = -INFINITY;
-            for (int o = lo; o <= hi; ++o) {
-                const int q = std::min(std::max(c + o, 0), n[ax] - 1);
-                m = fmaxf(m, a[i + (size_t)(q - c) * st[ax]]);
-            }
-            b[i] = m;
-        }
-        a.swap(b);
-    }
-    return a;
-}
-
 // The per-pixel proofs of dsdf_proof.h for every film-block pixel of one view (what k_pixel_skip computes), with the margins
-// the library would choose (skip_level / hit_step).  flags: (H+4) x (W+4) bytes; info[0] = empty-proof step, info[1] = hit-proof
-// step, info[2] = coarse level (0 where a proof is not available for this camera / grid).
+// the library would choose (ProofMargins).  flags: (H+4) x (W+4) bytes; info[0] = empty-proof step, info[1] = hit-proof
+// step, info[2] = coarse level (0 where a proof is not available for this camera / grid), info[3] = step of the fine hit proof.
 void hh_pixel_proof(const float *data, int rx, int ry, int rz, const dsdf_params *prm, const dsdf_camera *cam, int W, int H,
                     unsigned char *flags, float *info, int stages) {
     std::vector<float> p = pad(data, rx, ry, rz);
     GridView G = make_view(p.data(), rx, ry, rz, *prm);
-    float step = 0.f;
-    const int level = skip_level(cam, 1, W, rx, ry, rz, step);
-    const float hstep = (stages & 1) ? hit_step(cam, 1, W, rx, ry, rz) : 0.f;
-    const float fstep = (stages & 2) ? hit_step_fine(cam, 1, W, rx, ry, rz) : 0.f;
+    const ProofMargins M = proof_margins(cam, 1, W, rx, ry, rz);
+    const int level = M.level;
+    const float step = M.step, hstep = (stages & 1) ? M.hstep : 0.f, fstep = (stages & 2) ? M.fstep : 0.f;
     BoundGrid Bmin, Bmax, Bfine;
     std::vector<float> cmin, cmax, fine;
     if (fstep > 0.f) {
-        fine = window_max(data, rx, ry, rz, DSDF_FINE_LO, DSDF_FINE_HI);
-        Bfine.b = fine.data(); Bfine.cx = rx; Bfine.cy = ry; Bfine.cz = rz; Bfine.shift = 0; Bfine.off = 0.5f;
+        fine = window_max(data, rx, ry, rz);
+        Bfine = bound_grid(fine.data(), block_dims(rx, ry, rz, 0), 0, 0.5f);
     }
     if (level >= 0) {
-        cmin = block_bounds(data, rx, ry, rz, 1 << DSDF_COARSE_SHIFT(level), 1, false, Bmin.cx, Bmin.cy, Bmin.cz);
-        Bmin.b = cmin.data(); Bmin.shift = DSDF_COARSE_SHIFT(level); Bmin.off = 0.f;
+        cmin = block_bounds<false>(data, rx, ry, rz, DSDF_COARSE_SHIFT(level), 1, Bmin);
+        Bmin.b = cmin.data();
     }
-    cmax = block_bounds(data, rx, ry, rz, 1 << DSDF_HIT_SHIFT, DSDF_HIT_RADIUS, true, Bmax.cx, Bmax.cy, Bmax.cz);
-    Bmax.b = cmax.data(); Bmax.shift = DSDF_HIT_SHIFT; Bmax.off = 0.f;
+    cmax = block_bounds<true>(data, rx, ry, rz, DSDF_HIT_SHIFT, DSDF_HIT_RADIUS, Bmax);
+    Bmax.b = cmax.data();
     const int Wb = W + 2 * DSDF_BORDER, Hb = H + 2 * DSDF_BORDER;
     for (int py = 0; py < Hb; ++py)
         for (int px = 0; px < Wb; ++px) {
-            CamRay r = camera_ray(*cam, *prm, (float)(px - DSDF_BORDER) + 0.5f, (float)(py - DSDF_BORDER) + 0.5f, W, H);
-            V3 d = r.d * rsqf(dot(r.d, r.d));
-            unsigned f = (level >= 0 && step > 0.f) ? pixel_empty_proof(G, Bmin, *prm, r.o, d, step) : 0u;
-            if (level >= 0 && hstep > 0.f && !(f & DSDF_PX_EMPTY)) f |= pixel_hit_proof(G, Bmax, *prm, r.o, d, hstep);
-            if (level >= 0 && fstep > 0.f && !(f & (DSDF_PX_EMPTY | DSDF_PX_HIT))) f |= pixel_hit_proof(G, Bfine, *prm, r.o, d, fstep);
+            const CamRay r = pixel_centre_ray(*cam, *prm, px, py, W, H);
+            unsigned f = (level >= 0 && step > 0.f) ? pixel_empty_proof(G, Bmin, *prm, r.o, r.d, step) : 0u;
+            if (level >= 0 && hstep > 0.f && !(f & DSDF_PX_EMPTY)) f |= pixel_hit_proof(G, Bmax, *prm, r.o, r.d, hstep);
+            if (level >= 0 && fstep > 0.f && !(f & (DSDF_PX_EMPTY | DSDF_PX_HIT))) f |= pixel_hit_proof(G, Bfine, *prm, r.o, r.d, fstep);
             flags[(size_t)py * Wb + px] = (unsigned char)f;
         }
     info[0] = step; info[1] = hstep; info[2] = (float)level; info[3] = fstep;

@@ -1,6 +1,7 @@
 """Shared by tests/test_proof_fine_host.py and tests/test_gpu_proof_fine.py: the cases of the device-flag test
 (test_gpu_parity.py::test_device_proof_flags_match_host_proof) and the stand-alone host build of the second stage of the
-empty-space proof (tests/harness/dsdf_proof_fine_host.cpp)."""
+empty-space proof and of the third proof stage (tests/harness/dsdf_proof_stages_host.cpp; tests/proof_value_cases.py uses the same
+library and constants)."""
 import ctypes as C
 import functools
 import os
@@ -11,22 +12,23 @@ import numpy as np
 import sdf_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_proof_fine_host.cpp')
+SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_proof_stages_host.cpp')
 OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
 CASES = ['sphere64', 'blob64_flat', 'rag_x3']
 PX_EMPTY, PX_EMPTY_G, PX_HIT, PX_EMPTY_FINE = 1, 2, 16, 128
+PX_KEEP = PX_EMPTY | PX_EMPTY_G | PX_HIT | PX_EMPTY_FINE
 ICAM, NCAM = 2, 5
 
 
 @functools.lru_cache(None)
 def host_lib():
     os.makedirs(OUT, exist_ok=True)
-    out = os.path.join(OUT, 'libdsdf_proof_fine_host.so')
+    out = os.path.join(OUT, 'libdsdf_proof_stages_host.so')
     r = subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True)
     assert r.returncode == 0, r.stdout
     lib = C.CDLL(out)
-    lib.pfh_fine_empty.restype = C.c_float
+    lib.psh_fine_empty.restype = lib.psh_proofs.restype = C.c_float
     return lib
 
 
@@ -53,7 +55,7 @@ def fine_empty(params, grid, cam, W, H):
     rz, ry, rx = grid.shape
     flags = np.zeros((H + 4, W + 4), np.uint8)
     cam = np.ascontiguousarray(cam, np.float32)
-    step = host_lib().pfh_fine_empty(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, _p(flags))
+    step = host_lib().psh_fine_empty(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, _p(flags))
     return flags, float(step)
 
 
@@ -63,15 +65,24 @@ def sample_weights(params, grid, cam, W, H, spp, seed, mask):
     out = np.zeros((H + 4, W + 4, spp), np.uint8)
     cam = np.ascontiguousarray(cam, np.float32)
     mask = np.ascontiguousarray(mask, np.uint8)
-    host_lib().pfh_sample_weights(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, spp, C.c_uint(seed), _p(mask), _p(out))
-    return out
+    host_lib().psh_trace(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, spp, C.c_uint(seed), _p(mask), _p(out))
+    return out >> 1         # (psh_trace: bit 0 = the primal's march hits, then these two)
 
 
-def window_min(grid):
+def window(grid, maxi):
+    """Window minima / maxima (Z,Y,X) as the three separable passes build them."""
     rz, ry, rx = grid.shape
     out = np.zeros_like(grid)
-    host_lib().pfh_window_min(_p(grid), rx, ry, rz, _p(out))
+    host_lib().psh_window(_p(grid), rx, ry, rz, int(maxi), _p(out))
     return out
+
+
+def block_bounds(grid, shift, radius, maxi):
+    """(raw, dilated) block minima / maxima over blocks of (1 << shift)^3 voxels, each (ceil(rz / C), ceil(ry / C), ceil(rx / C))."""
+    rz, ry, rx = grid.shape
+    raw, dil = (np.zeros([-(-r >> shift) for r in grid.shape], np.float32) for _ in range(2))
+    host_lib().psh_block_bounds(_p(grid), rx, ry, rz, shift, radius, int(maxi), _p(raw), _p(dil))
+    return raw, dil
 
 
 _host_flags = {}

@@ -1,39 +1,18 @@
 """Shared by tests/test_proof_value_host.py and tests/test_gpu_proof_value.py: the stand-alone host build of the third proof stage
-(tests/proof_value_host.cpp: spline value on the centre ray -+ a gradient bound, csrc/dsdf_proof.h) on the cases of
+(tests/harness/dsdf_proof_stages_host.cpp: spline value on the centre ray -+ a gradient bound, csrc/dsdf_proof.h) on the cases of
 tests/proof_fine_cases.py plus one grid of plain random values, which is no SDF."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import sdf_oracle as O
 import proof_fine_cases as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'proof_value_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
+from proof_fine_cases import PX_EMPTY, PX_EMPTY_FINE, PX_EMPTY_G, PX_HIT, PX_KEEP, _p, host_lib
+
 NOISE = 'noise64'
 CASES = F.CASES + [NOISE]
-PX_EMPTY, PX_EMPTY_G, PX_HIT, PX_EMPTY_FINE = 1, 2, 16, 128
-PX_KEEP = PX_EMPTY | PX_EMPTY_G | PX_HIT | PX_EMPTY_FINE
-
-
-@functools.lru_cache(None)
-def host_lib():
-    os.makedirs(OUT, exist_ok=True)
-    out = os.path.join(OUT, 'libdsdf_proof_value_host.so')
-    r = subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True)
-    assert r.returncode == 0, r.stdout
-    lib = C.CDLL(out)
-    lib.pvh_proofs.restype = C.c_float
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @functools.lru_cache(None)
@@ -73,7 +52,7 @@ def host_flags(harness, name, want_hit=True, cam=None):
         rz, ry, rx = grid.shape
         two, merged, third = (np.zeros((H + 4, W + 4), np.uint8) for _ in range(3))
         info = np.zeros(4, np.float32)
-        step = host_lib().pvh_proofs(_p(grid), rx, ry, rz, C.byref(harness.params), _p(cam), W, H, _p(coarse), int(want_hit), _p(two), _p(merged),
+        step = host_lib().psh_proofs(_p(grid), rx, ry, rz, C.byref(harness.params), _p(cam), W, H, _p(coarse), int(want_hit), _p(two), _p(merged),
                                      _p(third), _p(info))
         assert step > 0
         out = dict(coarse=coarse, two=two, merged=merged, third=third, info=(float(step),) + tuple(float(v) for v in info))
@@ -92,7 +71,7 @@ def trace(params, name, spp, seed, mask):
     rz, ry, rx = grid.shape
     out = np.zeros((H + 4, W + 4, spp), np.uint8)
     mask = np.ascontiguousarray(mask, np.uint8)
-    host_lib().pvh_trace(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, spp, C.c_uint(seed), _p(mask), _p(out))
+    host_lib().psh_trace(_p(grid), rx, ry, rz, C.byref(params), _p(cam), W, H, spp, C.c_uint(seed), _p(mask), _p(out))
     return out
 
 

@@ -1,5 +1,5 @@
 """CPU check of the THIRD proof stage (csrc/dsdf_proof.h: the spline value on the centre ray -+ a gradient bound, ValueBound /
-pixel_fine_proofs) through a stand-alone host build of its own (tests/proof_value_host.cpp), against traced sample rays: every sample
+pixel_fine_proofs) through the stand-alone host build of the fine stages (tests/harness/dsdf_proof_stages_host.cpp), against traced sample rays: every sample
 of a pixel the stage newly proves empty must miss, of one it proves gradient-empty must also carry a zero boundary weight, of one it
 proves hit must hit.  The render kernels skip the march of such pixels, so a single counter-example would be a wrong image or
 gradient: zero violations, no tolerance.  Cases: those of tests/proof_fine_cases.py and one grid of plain random values, no SDF,
@@ -19,7 +19,7 @@ def test_gradient_bound_is_the_largest_tap_difference():
     import ctypes as C
     D = np.zeros(3, np.float32)
     rz, ry, rx = grid.shape
-    host_lib().pvh_tap_diff_max(grid.ctypes.data_as(C.c_void_p), rx, ry, rz, D.ctypes.data_as(C.c_void_p))
+    host_lib().psh_tap_diff_max(grid.ctypes.data_as(C.c_void_p), rx, ry, rz, D.ctypes.data_as(C.c_void_p))
     ref = [np.abs(np.diff(grid, axis=ax)).max() for ax in (2, 1, 0)]
     assert D.tolist() == [float(v) for v in ref]
 

@@ -8,7 +8,7 @@ axis: all >= 0, sum 1), so for every y within r voxels of x
 
     |v(y) - v(x)| <= r * |(D_x, D_y, D_z)|_2          (voxel units; D_a = largest |tap difference| along axis a the lookups can touch)
 
-with r = lateral deviation + half a step (< 1 voxel: hit_step_fine).  This replays, on bench views, the proofs with the bound
+with r = lateral deviation + half a step (< 1 voxel: ProofMargins::fstep).  This replays, on bench views, the proofs with the bound
 max(window minimum, v(x) - r |D|) (empty) and min(window maximum, v(x) + r |D|) (hit) in the unchanged logic of pixel_empty_proof /
 pixel_hit_proof, for several representations of D: one global figure, per block of 8^3 / 4^3 voxels dilated by one block, and per cell
 (the exact 6^3 window: the best any representation can do).  It weighs the pixels each settles by the steps the fp32 C oracle needs for
