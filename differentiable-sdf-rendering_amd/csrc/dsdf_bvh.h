@@ -290,6 +290,14 @@ DSDF_HD V3 bvh_normal(const BvhView &B, const BvhHit &h) {
     return n * (1.f / sqrtf(dot(n, n)));
 }
 
+// the reflectance of a hit from the colours per triangle corner (n_triangles x 9: rgb of p0, p1, p2, in the CALLER's triangle order --
+// indexed by the original index, not by the slot): the barycentric interpolation (1 - u - v) c0 + u c1 + v c2
+DSDF_HD void bvh_corner_color(const float *corner_colors, const BvhHit &h, float rgb[3]) {
+    const float *q = corner_colors + (size_t)9 * h.prim;
+    const float w = 1.f - h.u - h.v;
+    for (int c = 0; c < 3; ++c) rgb[c] = w * q[c] + h.u * q[3 + c] + h.v * q[6 + c];
+}
+
 }  // namespace dsdf
 
 #if defined(__HIPCC__)
@@ -397,9 +405,11 @@ __global__ __launch_bounds__(256) void k_bvh_level(float *__restrict__ bvh, uint
 // One lane per film sample in the reference's lane order (reparam.py:140-155): camera ray, closest hit, the primal `sample()`
 // statement of the integrator with the intersection routine swapped (no warp, det = 1), re-projection of o + d, film splat.
 // spp % 64 == 0: a wave is 64 samples of one pixel and reduces its 5 x 5 window before it touches memory (film_accum_wave).
-template <int NCH>
-__global__ __launch_bounds__(DSDF_BLOCK) void k_mesh_render(const float *__restrict__ bvh, dsdf_params P, ViewBatch VB, float *__restrict__ blocks,
-                                                            uint32_t n_lanes, ShadeArgs S) {
+// COLORS (DSDF_DIRECT only): the reflectance comes from `corner_colors` (bvh_corner_color) and S.albedo is not read; the instantiations
+// without it never touch the pointer.
+template <int NCH, bool COLORS>
+__global__ __launch_bounds__(DSDF_BLOCK) void k_mesh_render(const float *__restrict__ bvh, const float *__restrict__ corner_colors, dsdf_params P,
+                                                            ViewBatch VB, float *__restrict__ blocks, uint32_t n_lanes, ShadeArgs S) {
     __shared__ float4 top[DSDF_BVH_LDS_FLOAT4];
     __shared__ __attribute__((aligned(16))) float film_lds[DSDF_BLOCK / 64][DSDF_TROWS * DSDF_TSTRIDE];
     const ViewArgs &A = VB.v[blockIdx.y];
@@ -435,7 +445,8 @@ __global__ __launch_bounds__(DSDF_BLOCK) void k_mesh_render(const float *__restr
                 EmitterTerm e;
                 emitter_term(S, dh, d, e);
                 float alb[3]; V3 ag[3];
-                eval_trilinear(S.albedo, dh.p, alb, ag);
+                if (COLORS) bvh_corner_color(corner_colors, h, alb);
+                else eval_trilinear(S.albedo, dh.p, alb, ag);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) vals[c] = (alb[c] * e.ke + e.ks) * S.env[c];
             }
@@ -486,16 +497,19 @@ size_t dsdf_mesh_render_workspace_size(int width, int height, int n_views) {
     return (size_t)(n_views < DSDF_MAX_BATCH ? n_views : DSDF_MAX_BATCH) * (width + 2 * DSDF_BORDER) * (height + 2 * DSDF_BORDER) * 4 * sizeof(float);
 }
 
-int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsdf_camera *cams, int n_views, int width, int height, int spp,
-                             const float *offsets, const uint32_t *seeds, int integrator, const dsdf_shading *shading, float *image_out,
-                             void *workspace, size_t workspace_bytes, void *stream) {
+// (the error texts keep the name of the call the two entry points share)
+int dsdf_mesh_render_forward_colors(const float *bvh, const float *corner_colors, const dsdf_params *prm, const dsdf_camera *cams, int n_views,
+                                    int width, int height, int spp, const float *offsets, const uint32_t *seeds, int integrator,
+                                    const dsdf_shading *shading, float *image_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (!bvh || !prm || !cams || !image_out || !workspace) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: null pointer argument");
     if (n_views < 1 || width < 1 || height < 1 || spp < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: non-positive size argument");
     if (integrator != DSDF_SILHOUETTE && integrator != DSDF_SIMPLE_SHADING && integrator != DSDF_DIRECT)
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: unknown integrator id");
     const bool direct = integrator == DSDF_DIRECT;
-    if (direct && (!shading || !shading->albedo || shading->ax < 1 || shading->ay < 1 || shading->az < 1))
-        return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: sdf_direct_reparam needs a dsdf_shading with an albedo volume");
+    const bool colors = direct && corner_colors;             // (the other integrators have no reflectance: the colours are ignored)
+    if (direct && (!shading || (!colors && (!shading->albedo || shading->ax < 1 || shading->ay < 1 || shading->az < 1))))
+        return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: sdf_direct_reparam needs a dsdf_shading with an albedo volume"
+                                          " (or, with corner colours, a dsdf_shading for the emitter)");
     if (direct && (shading->bsdf != 0 || shading->use_mis != 0))
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: a mesh is rendered with the diffuse BSDF and emitter sampling only (bsdf = 0, use_mis = 0)");
     if (!offsets && !seeds) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_render_forward: need offsets or seeds");
@@ -512,7 +526,7 @@ int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsd
     memset(&S, 0, sizeof(S));
     const float *emitter_u = nullptr;
     if (direct) {
-        S.albedo.data = shading->albedo; S.albedo.rx = shading->ax; S.albedo.ry = shading->ay; S.albedo.rz = shading->az;
+        if (!colors) { S.albedo.data = shading->albedo; S.albedo.rx = shading->ax; S.albedo.ry = shading->ay; S.albedo.rz = shading->az; }
         for (int k = 0; k < 3; ++k) S.env[k] = shading->env_radiance[k];
         S.hide_emitters = shading->hide_emitters;
         emitter_u = shading->emitter_samples;
@@ -527,12 +541,20 @@ int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsd
                                      0, *prm, emitter_u ? emitter_u + v * nl * 2 : nullptr);
         }
         if (hipMemsetAsync(blocks, 0, nv * per_view, st) != hipSuccess) return fail(DSDF_ERR_LAUNCH, "dsdf_mesh_render_forward: hipMemsetAsync(film block) failed");
-        int rc = launch("k_mesh_render", direct ? k_mesh_render<4> : k_mesh_render<2>, dim3((unsigned)((nl + DSDF_BLOCK - 1) / DSDF_BLOCK), nv),
-                        dim3(DSDF_BLOCK), st, bvh, *prm, VB, blocks, (uint32_t)nl, S);
+        int rc = launch("k_mesh_render", colors ? k_mesh_render<4, true> : (direct ? k_mesh_render<4, false> : k_mesh_render<2, false>),
+                        dim3((unsigned)((nl + DSDF_BLOCK - 1) / DSDF_BLOCK), nv), dim3(DSDF_BLOCK), st, bvh, colors ? corner_colors : nullptr, *prm,
+                        VB, blocks, (uint32_t)nl, S);
         if (rc) return rc;
         if ((rc = develop(blocks, nv, width, height, direct, image_out + v0 * (size_t)width * height * 3, st))) return rc;
     }
     return DSDF_OK;
+}
+
+int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsdf_camera *cams, int n_views, int width, int height, int spp,
+                             const float *offsets, const uint32_t *seeds, int integrator, const dsdf_shading *shading, float *image_out,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+    return dsdf_mesh_render_forward_colors(bvh, nullptr, prm, cams, n_views, width, height, spp, offsets, seeds, integrator, shading, image_out,
+                                           workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -206,10 +206,30 @@ DSDF_HD void iso_refine_vertex(const GridView &G, const IsoLattice &L, const flo
     }
 }
 
+// ---- colours for the vertices: the value of a (Z,Y,X,channels) volume at a point, channels 1 or 3 ----------------------------------
+// What the direct integrator reads there: eval_trilinear / eval_trilinear1 (dsdf_math.h) with the gradient dropped.
+DSDF_HD void volume_sample_point(const AlbedoView &A, int channels, const float *points, int64_t i, float *out) {
+    const V3 p = mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+    if (channels == 3) {
+        float val[3]; V3 grad[3];
+        eval_trilinear(A, p, val, grad);
+        out[3 * i] = val[0]; out[3 * i + 1] = val[1]; out[3 * i + 2] = val[2];
+    } else {
+        float val; V3 grad;
+        eval_trilinear1(A, p, val, grad);
+        out[i] = val;
+    }
+}
+
 }  // namespace dsdf
 
 #if defined(__HIPCC__)
 using namespace dsdf;
+
+__global__ __launch_bounds__(256) void k_volume_sample(AlbedoView A, int channels, const float *__restrict__ points, int64_t n, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) volume_sample_point(A, channels, points, i, out);
+}
 
 __global__ __launch_bounds__(256) void k_iso_sample(GridView G, IsoLattice L, int n_nodes, float *__restrict__ values) {
     const int node = blockIdx.x * 256 + threadIdx.x;
@@ -297,6 +317,18 @@ int dsdf_iso_refine(const float *padded, int rx, int ry, int rz, const float *va
     if (n_vert > 7 * iso_node_count(nx, ny, nz)) return fail(DSDF_ERR_INVALID_ARG, "dsdf_iso_refine: more vertices than the lattice has edges");
     return launch("k_iso_refine", k_iso_refine, dim3((unsigned)((n_vert + 255) / 256)), dim3(256), (hipStream_t)stream, iso_view(padded, rx, ry, rz),
                   iso_lattice(nx, ny, nz), values, iso, vert_edge, n_vert, steps, positions, normals);
+}
+
+int dsdf_volume_sample(const float *volume, int vx, int vy, int vz, int channels, const float *points, int64_t n, float *out, void *stream) {
+    if (channels != 1 && channels != 3) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: channels must be 1 or 3");
+    if (vx < 1 || vy < 1 || vz < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: bad volume size");
+    if (n < 0 || n > (int64_t)256 * 0x7fffffff) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: bad point count");
+    if (!volume) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: null pointer argument");
+    if (n == 0) return DSDF_OK;
+    if (!points || !out) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: null pointer argument");
+    AlbedoView A;
+    A.data = volume; A.rx = vx; A.ry = vy; A.rz = vz;
+    return launch("k_volume_sample", k_volume_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, A, channels, points, n, out);
 }
 
 }  // extern "C"

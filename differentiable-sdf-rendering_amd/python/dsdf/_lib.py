@@ -107,6 +107,10 @@ SYMBOLS = {
     'dsdf_mesh_render_forward': (C.c_int, [C.c_void_p, C.POINTER(DsdfParams), C.POINTER(DsdfCamera), C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(DsdfShading), C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p]),
+    'dsdf_mesh_render_forward_colors': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DsdfParams), C.POINTER(DsdfCamera), C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(DsdfShading), C.c_void_p,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    'dsdf_volume_sample': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'dsdf_iso_sample': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'dsdf_iso_mark': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'dsdf_iso_emit': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

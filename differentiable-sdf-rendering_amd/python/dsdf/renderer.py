@@ -224,7 +224,9 @@ class Shading:
     decouple_reparam: the integrator properties of the same names (sdf_direct_reparam.py:13-14, 44-47).
     roughness (Z,Y,X,1): switches the BSDF to `principled` at the plugin defaults -- `albedo` is then its base_color volume and
     `roughness` 'main-bsdf.roughness.volume.data' (python/opt_configs.py:288-299); a gradient call accumulates dL/d(roughness)
-    into `grad_roughness` (a tensor shaped like roughness, set on the object) next to grad_albedo."""
+    into `grad_roughness` (a tensor shaped like roughness, set on the object) next to grad_albedo.
+    albedo=None is legal for dsdf.mesh_render of a MeshBvh that carries corner colours (they are the reflectance then); every other
+    entry point refuses it."""
 
     def __init__(self, albedo, env_radiance=(1.0, 1.0, 1.0), hide_emitters=False, use_mis=False, detach_indirect_si=False,
                  decouple_reparam=False, roughness=None):
@@ -240,19 +242,25 @@ class Shading:
         return Shading(albedo, self.env_radiance, self.hide_emitters, self.use_mis, self.detach_indirect_si, self.decouple_reparam,
                        self.roughness)
 
-    def to_struct(self, n_views, n_lanes, emitter_samples=None, grad_albedo=None, bsdf_samples=None):
-        a = self.albedo.detach()
-        if a.dim() != 4 or a.shape[3] != 3:
-            raise _lib.DsdfError(f"albedo must be (Z,Y,X,3), got {tuple(a.shape)}")
-        a = _require_dev(a, 'albedo')
+    def to_struct(self, n_views, n_lanes, emitter_samples=None, grad_albedo=None, bsdf_samples=None, need_albedo=True):
         st = DsdfShading()
-        st.albedo = a.data_ptr()
-        st.az, st.ay, st.ax = (int(v) for v in a.shape[:3])
+        keep = []
+        if self.albedo is None:
+            if need_albedo or grad_albedo is not None:
+                raise _lib.DsdfError("Shading(albedo=None) serves dsdf.mesh_render of a MeshBvh with corner colours only: this call reads "
+                                     "the reflectance volume, pass albedo (Z,Y,X,3)")
+        else:
+            a = self.albedo.detach()
+            if a.dim() != 4 or a.shape[3] != 3:
+                raise _lib.DsdfError(f"albedo must be (Z,Y,X,3), got {tuple(a.shape)}")
+            a = _require_dev(a, 'albedo')
+            st.albedo = a.data_ptr()
+            st.az, st.ay, st.ax = (int(v) for v in a.shape[:3])
+            keep.append(a)
         st.env_radiance[0], st.env_radiance[1], st.env_radiance[2] = self.env_radiance
         st.hide_emitters = int(self.hide_emitters)
         st.use_mis = int(self.use_mis)
         st.variant = 1 if self.detach_indirect_si else (2 if self.decouple_reparam else 0)   # (the reference tests them in this order)
-        keep = [a]
         for name, t in (('emitter_samples', emitter_samples), ('bsdf_samples', bsdf_samples)):
             if t is None:
                 continue
@@ -833,9 +841,11 @@ def mesh_raycast(triangles, rays_o, rays_d, t_min=0.0):
 class MeshBvh:
     """A bounding-volume hierarchy over a triangle soup in one device buffer (include/dsdf.h: the layout is ABI): Morton codes of
     the centroids (dsdf_mesh_morton), a stable torch sort -- plumbing -- and the build (dsdf_mesh_bvh_build).  `triangles`
-    (T,3,3) and the optional per-corner `normals` (T,3,3) are device tensors; with normals the mesh renders smooth-shaded."""
+    (T,3,3) and the optional per-corner `normals` (T,3,3) are device tensors; with normals the mesh renders smooth-shaded.
+    `colors` (T,3,3): a linear reflectance (rgb) per triangle corner, kept beside the buffer as `.colors` in the caller's triangle order
+    (the kernel looks them up by original index); dsdf.mesh_render shades sdf_direct_reparam with them instead of a reflectance volume."""
 
-    def __init__(self, triangles, normals=None):
+    def __init__(self, triangles, normals=None, colors=None):
         lib = _lib.load()
         tri = _require_dev(triangles.reshape(-1, 9), 'triangles')
         T = int(tri.shape[0])
@@ -846,6 +856,13 @@ class MeshBvh:
             nrm = _require_dev(normals.reshape(-1, 9), 'normals')
             if nrm.shape[0] != T:
                 raise _lib.DsdfError(f"normals must be (T,3,3) like triangles, got {tuple(normals.shape)}")
+        self.colors = None
+        if colors is not None:
+            if tuple(colors.shape) != (T, 3, 3):
+                raise _lib.DsdfError(f"colors must be (T,3,3) like triangles, got {tuple(colors.shape)}")
+            self.colors = _require_dev(colors, 'colors')
+            if self.colors.device != tri.device:
+                raise _lib.DsdfError("colors must live on the device of the triangles")
         self.device, self.n_triangles, self.has_normals = tri.device, T, nrm is not None
         self.buffer = torch.empty(int(lib.dsdf_mesh_bvh_size(T, int(nrm is not None))), dtype=torch.float32, device=tri.device)
         codes = torch.empty(T, dtype=torch.int32, device=tri.device)
@@ -873,7 +890,9 @@ def mesh_render(bvh, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SIL
                 params=None):
     """Primal render of a triangle mesh (dsdf_mesh_render_forward): render_forward with the intersection routine swapped -- the
     reference images of a mesh scene (python/optimize.py:11-40) -> (n_views, H, W, 3).  `shading` (dsdf.Shading, diffuse, no
-    use_mis) and `emitter_samples` belong to sdf_direct_reparam; `params` carries the clip planes and the light direction."""
+    use_mis) and `emitter_samples` belong to sdf_direct_reparam; `params` carries the clip planes and the light direction.
+    A `bvh` with corner colours (MeshBvh(..., colors=)) takes the reflectance of sdf_direct_reparam from them
+    (dsdf_mesh_render_forward_colors): shading.albedo is not read then and may be None."""
     lib = _lib.load()
     sensors, cams, W, H = _views(sensors)
     nv, spp = len(sensors), int(spp)
@@ -881,29 +900,53 @@ def mesh_render(bvh, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SIL
     offsets, cseeds = _sampler_args(nv, seeds, offsets, n_lanes)
     integ = INTEGRATORS[integrator]
     prm = params if params is not None else _lib.default_params()
-    sh = keep = None
+    sh = keep = colors = None
     if integ == DSDF_DIRECT:
         if shading is None:
             raise _lib.DsdfError("sdf_direct_reparam needs shading=dsdf.Shading(albedo, ...)")
-        st, keep = shading.to_struct(nv, n_lanes, emitter_samples)
+        colors = bvh.colors
+        st, keep = shading.to_struct(nv, n_lanes, emitter_samples, need_albedo=colors is None)
         sh = C.byref(st)
     dev = bvh.device
     img = torch.empty(nv, H, W, 3, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.dsdf_mesh_render_workspace_size(W, H, min(nv, MAX_VIEWS_PER_LAUNCH)), lib.dsdf_mesh_render_workspace_size(W, H, 1))
     with torch.cuda.device(dev):
-        _lib.check(lib.dsdf_mesh_render_forward(_ptr(bvh.buffer), C.byref(prm), cams, nv, W, H, spp, _ptr(offsets), cseeds, integ, sh,
-                                                _ptr(img), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(lib.dsdf_mesh_render_forward_colors(_ptr(bvh.buffer), _ptr(colors), C.byref(prm), cams, nv, W, H, spp, _ptr(offsets), cseeds,
+                                                       integ, sh, _ptr(img), _ptr(ws), ws.numel(), _stream()))
     return img
 
 
-def extract_mesh(grid, resolution=None, iso=0.0, steps=24, normals=True):
+def sample_volume(volume, points):
+    """Trilinear lookup of a volume on the unit cube, (Z,Y,X,C) or (Z,Y,X) with C = 1 or 3, at `points` (N,3) in the volume's frame ->
+    (N,C) (dsdf_volume_sample): the value the direct integrator reads there from a reflectance or roughness volume."""
+    lib = _lib.load()
+    vol = volume.detach()
+    if vol.dim() == 3:
+        vol = vol[..., None]
+    if vol.dim() != 4 or vol.shape[3] not in (1, 3):
+        raise _lib.DsdfError(f"volume must be (Z,Y,X) or (Z,Y,X,C) with C = 1 or 3, got {tuple(volume.shape)}")
+    vol = _require_dev(vol, 'volume')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.DsdfError(f"points must be (N,3), got {tuple(points.shape)}")
+    pts = _require_dev(points, 'points')
+    vz, vy, vx, ch = (int(v) for v in vol.shape)
+    n = int(pts.shape[0])
+    out = torch.empty(n, ch, dtype=torch.float32, device=vol.device)
+    with torch.cuda.device(vol.device):
+        _lib.check(lib.dsdf_volume_sample(_ptr(vol), vx, vy, vz, ch, _ptr(pts), n, _ptr(out), _stream()))
+    return out
+
+
+def extract_mesh(grid, resolution=None, iso=0.0, steps=24, normals=True, colors=None):
     """Triangle mesh of the surface the renderer sees: the level set {f = iso} of the grid's tricubic lookup f, by marching tetrahedra
     on a lattice of `resolution` (an int or (nx, ny, nz); default: the grid's own) cells, every vertex moved onto the root of f on its
     lattice edge by `steps` bisection steps (include/dsdf.h: dsdf_iso_*, csrc/dsdf_iso.h) -> (vertices (V, 3) float32, faces (F, 3)
     int32[, normals (V, 3)]) on the grid's device, in WORLD space: the library works in the cube's own frame, `+ sdf.p` and a general
     to_world (normals through its inverse transpose) are applied here.  Faces wind so that their normal points towards larger f.
     `vertices[faces.long()]` with `normals[faces.long()]` is what dsdf.MeshBvh takes.  A surface that leaves the cube stays open there;
-    no surface gives V = F = 0.  The two exclusive scans between the launches are torch.cumsum (plumbing), and their totals are read
+    no surface gives V = F = 0.  `colors`: a reflectance volume (Z,Y,X,3) on the device -- the tuple gains a last element (V, 3), its
+    trilinear lookup (sample_volume) at the WORLD-space vertices returned (the volume lives in world space: what the direct integrator
+    reads at that point of the surface).  The two exclusive scans between the launches are torch.cumsum (plumbing), and their totals are read
     back once to size the outputs -- the call synchronises there."""
     lib = _lib.load()                                      # (cube coordinates in either build: the default one serves every grid)
     if resolution is None:
@@ -941,7 +984,12 @@ def extract_mesh(grid, resolution=None, iso=0.0, steps=24, normals=True):
         if nrm is not None:
             nrm = torch.nn.functional.normalize(nrm.double() @ torch.linalg.inv(tw[:3, :3]), dim=1).float()
     pos = pos + torch.tensor([float(v) for v in grid.params.sdf_p], dtype=torch.float32, device=dev)
-    return (pos, faces, nrm) if normals else (pos, faces)
+    out = (pos, faces, nrm) if normals else (pos, faces)
+    if colors is not None:
+        if colors.dim() != 4 or colors.shape[3] != 3:
+            raise _lib.DsdfError(f"colors must be a reflectance volume (Z,Y,X,3), got {tuple(colors.shape)}")
+        out += (sample_volume(colors, pos),)
+    return out
 
 
 def kernel_timing_arm():

@@ -1,6 +1,8 @@
-"""`python extract_mesh.py <file.vol> [-o out.ply|out.obj] [--res N] [--iso v]`: the triangle mesh of the surface the renderer sees in
-an SDF checkpoint (the `.vol` files optimize.py writes) -- dsdf.extract_mesh on util.read_vol, written by mesh_to_sdf.save_ply /
-save_obj with the vertex normals.  The mesh lives in the unit cube of the grid, like the SDF."""
+"""`python extract_mesh.py <file.vol> [-o out.ply|out.obj] [--res N] [--iso v] [--albedo <file.vol> [--float-colors]]`: the triangle
+mesh of the surface the renderer sees in an SDF checkpoint (the `.vol` files optimize.py writes) -- dsdf.extract_mesh on util.read_vol,
+written by mesh_to_sdf.save_ply / save_obj with the vertex normals.  The mesh lives in the unit cube of the grid, like the SDF.
+--albedo: the reflectance checkpoint of a textured reconstruction (three channels); its value at every vertex is written as the vertex
+colour (linear, no gamma) -- uchar in a ply unless --float-colors."""
 import argparse
 import os
 import sys
@@ -17,6 +19,8 @@ def main(argv=None):
     ap.add_argument('--res', type=int, default=None, help="cells per axis of the extraction lattice (default: the grid's own resolution)")
     ap.add_argument('--iso', type=float, default=0.0, help='level to extract (default 0)')
     ap.add_argument('--steps', type=int, default=24, help='bisection steps per vertex (1 ... 32)')
+    ap.add_argument('--albedo', default=None, help='reflectance volume (three channels): baked onto the vertices as vertex colours')
+    ap.add_argument('--float-colors', action='store_true', help='ply: store the colours as float (lossless) instead of uchar')
     args = ap.parse_args(argv)
     out = args.output or os.path.splitext(args.vol)[0] + '.ply'
     if not out.endswith(('.ply', '.obj')):
@@ -25,8 +29,18 @@ def main(argv=None):
     if data.dim() != 3:
         ap.error(f'{args.vol}: expected a one-channel volume, got shape {tuple(data.shape)}')
     grid = dsdf.SdfGrid(data.float().contiguous())
-    v, f, n = dsdf.extract_mesh(grid, resolution=args.res, iso=args.iso, steps=args.steps)
-    (mesh_to_sdf.save_obj if out.endswith('.obj') else mesh_to_sdf.save_ply)(out, v, f, n)
+    albedo = None
+    if args.albedo is not None:
+        albedo = util.read_vol(args.albedo)
+        if albedo.dim() != 4 or albedo.shape[3] != 3:
+            ap.error(f'{args.albedo}: expected a three-channel volume, got shape {tuple(albedo.shape)}')
+        albedo = albedo.float().contiguous()
+    v, f, n, *c = dsdf.extract_mesh(grid, resolution=args.res, iso=args.iso, steps=args.steps, colors=albedo)
+    c = c[0] if c else None
+    if out.endswith('.obj'):
+        mesh_to_sdf.save_obj(out, v, f, n, colors=c)
+    else:
+        mesh_to_sdf.save_ply(out, v, f, n, colors=c, color_dtype='float' if args.float_colors else 'uchar')
     print(f'{out}: {v.shape[0]} vertices, {f.shape[0]} faces')
     return 0
 

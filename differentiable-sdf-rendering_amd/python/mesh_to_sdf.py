@@ -17,9 +17,10 @@ ANGULAR_RES = 16            # mesh_to_sdf.py:40: 16 x 16 stratified directions p
 BVH_MIN_TRIANGLES = 4096    # accel=None: meshes above this go through dsdf.MeshBvh, smaller ones through the brute-force kernel
 
 
-def load_obj(fn):
-    """Vertices / faces of a Wavefront obj (positions only; polygons are fan-triangulated, negative indices resolved)."""
-    v, f = [], []
+def load_obj(fn, colors=False):
+    """Vertices / faces of a Wavefront obj (positions only; polygons are fan-triangulated, negative indices resolved).  colors: a third
+    element, the (V, 3) float32 vertex colours of `v x y z r g b` lines, or None unless every vertex carries one."""
+    v, f, c = [], [], []
     with open(fn) as fh:
         for line in fh:
             s = line.split()
@@ -27,6 +28,8 @@ def load_obj(fn):
                 continue
             if s[0] == 'v':
                 v.append([float(s[1]), float(s[2]), float(s[3])])
+                if len(s) >= 7:
+                    c.append([float(s[4]), float(s[5]), float(s[6])])
             elif s[0] == 'f':
                 idx = []
                 for tok in s[1:]:
@@ -34,15 +37,26 @@ def load_obj(fn):
                     idx.append(k - 1 if k > 0 else len(v) + k)
                 for j in range(1, len(idx) - 1):
                     f.append([idx[0], idx[j], idx[j + 1]])
-    return np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3)
+    v, f = np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3)
+    if not colors:
+        return v, f
+    return v, f, (np.asarray(c, np.float32).reshape(-1, 3) if len(c) == len(v) and len(v) else None)
 
 
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
               'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
 
 
-def load_ply(fn):
-    """Vertices / faces of a ply file (ascii, binary_little_endian or binary_big_endian; x y z + one index list per face)."""
+def _ply_color_scale(type_name):
+    """What a stored colour component is divided by: an integer type spans [0, max], a float type is the value itself."""
+    dt = np.dtype(_PLY_TYPES[type_name])
+    return float(np.iinfo(dt).max) if dt.kind in 'iu' else 1.0
+
+
+def load_ply(fn, colors=False):
+    """Vertices / faces of a ply file (ascii, binary_little_endian or binary_big_endian; x y z + one index list per face).  colors: a
+    third element, the (V, 3) float32 vertex colours of the properties `red green blue` (uchar divided by 255, float as stored), or
+    None when the file has none."""
     with open(fn, 'rb') as fh:
         if fh.readline().strip() != b'ply':
             raise ValueError(f'{fn}: not a ply file')
@@ -65,7 +79,7 @@ def load_ply(fn):
         if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
             raise ValueError(f'{fn}: unsupported ply format {fmt}')
         en = '>' if fmt == 'binary_big_endian' else '<'
-        verts, faces = None, []
+        verts, faces, cols = None, [], None
         tokens = None
         if fmt == 'ascii':
             tokens = iter(fh.read().split())
@@ -106,6 +120,13 @@ def load_ply(fn):
                 else:
                     ix = [names.index(c) for c in 'xyz']
                     verts = np.asarray([[r[i] for i in ix] for r in rows], np.float32).reshape(-1, 3)
+                if all(c in names for c in ('red', 'green', 'blue')):
+                    chans = []
+                    for c in ('red', 'green', 'blue'):
+                        i = names.index(c)
+                        col = rows[c] if isinstance(rows, np.ndarray) else np.asarray([r[i] for r in rows], np.float64)
+                        chans.append(col.astype(np.float64) / _ply_color_scale(props[i][0]))
+                    cols = np.stack(chans, -1).astype(np.float32).reshape(-1, 3)
             elif name == 'face':
                 li = [i for i, p in enumerate(props) if p[0] == 'list'][0]
                 for r in rows:
@@ -114,10 +135,11 @@ def load_ply(fn):
                         faces.append([idx[0], idx[j], idx[j + 1]])
         if verts is None:
             raise ValueError(f'{fn}: no vertex element')
-    return verts, np.asarray(faces, np.int64).reshape(-1, 3)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    return (verts, faces, cols) if colors else (verts, faces)
 
 
-def _mesh_arrays(vertices, faces, normals):
+def _mesh_arrays(vertices, faces, normals, colors=None):
     def host(a, dt):
         a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
         return np.ascontiguousarray(a, dt).reshape(-1, 3)
@@ -127,31 +149,62 @@ def _mesh_arrays(vertices, faces, normals):
         raise ValueError(f'normals must be (V, 3) like vertices, got {n.shape}')
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError('face index out of range')
-    return v, f, n
+    if colors is None:
+        return v, f, n
+    c = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
+    if c.shape != v.shape:
+        raise ValueError(f'colors must be (V, 3) like vertices, got {c.shape}')
+    return v, f, n, np.ascontiguousarray(c, '<f4')
 
 
-def save_ply(fn, vertices, faces, normals=None):
+def save_ply(fn, vertices, faces, normals=None, colors=None, color_dtype='uchar'):
     """Writes an indexed triangle mesh (what dsdf.extract_mesh returns: tensors or arrays) as binary little-endian ply: x y z
-    [nx ny nz] per vertex, one uchar-counted int list per face.  load_ply reads it back."""
-    v, f, n = _mesh_arrays(vertices, faces, normals)
-    props = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if n is not None else [])
-    head = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + [f'property float {c}' for c in props] + \
+    [nx ny nz] [red green blue] per vertex, one uchar-counted int list per face.  load_ply reads it back.
+    colors (V, 3): LINEAR reflectance, written as it is -- no gamma is applied, a viewer that expects sRGB shows it darker.
+    color_dtype 'uchar' stores round(clip(c, 0, 1) * 255), what mesh viewers read; 'float' stores the values losslessly."""
+    if color_dtype not in ('uchar', 'float'):
+        raise ValueError(f"color_dtype must be 'uchar' or 'float', got {color_dtype!r}")
+    c = None
+    if colors is None:
+        v, f, n = _mesh_arrays(vertices, faces, normals)
+    else:
+        v, f, n, c = _mesh_arrays(vertices, faces, normals, colors)
+    fields = [('p', '<f4', (3,))] + ([('n', '<f4', (3,))] if n is not None else [])
+    props = [f'property float {k}' for k in ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if n is not None else [])]
+    if c is not None:
+        fields.append(('c', 'u1' if color_dtype == 'uchar' else '<f4', (3,)))
+        props += [f'property {color_dtype} {k}' for k in ('red', 'green', 'blue')]
+    head = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + props + \
            [f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']
+    vrec = np.zeros(len(v), np.dtype(fields))
+    vrec['p'] = v
+    if n is not None:
+        vrec['n'] = n
+    if c is not None:
+        vrec['c'] = np.rint(np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0).astype('u1') if color_dtype == 'uchar' else c
     rec = np.zeros(len(f), np.dtype([('k', 'u1'), ('i', '<i4', (3,))]))
     rec['k'] = 3
     rec['i'] = f
     with open(fn, 'wb') as fh:
         fh.write(('\n'.join(head) + '\n').encode('ascii'))
-        fh.write((v if n is None else np.concatenate([v, n], 1)).astype('<f4').tobytes())
+        fh.write(vrec.tobytes())
         fh.write(rec.tobytes())
     return fn
 
 
-def save_obj(fn, vertices, faces, normals=None):
-    """The same mesh as a Wavefront obj (v [vn] f, 1-based; 9 significant digits: float32 round-trips).  load_obj reads it back."""
-    v, f, n = _mesh_arrays(vertices, faces, normals)
+def save_obj(fn, vertices, faces, normals=None, colors=None):
+    """The same mesh as a Wavefront obj (v [vn] f, 1-based; 9 significant digits: float32 round-trips).  load_obj reads it back.
+    colors (V, 3): linear reflectance (no gamma), written as `v x y z r g b`."""
+    c = None
+    if colors is None:
+        v, f, n = _mesh_arrays(vertices, faces, normals)
+    else:
+        v, f, n, c = _mesh_arrays(vertices, faces, normals, colors)
     with open(fn, 'w') as fh:
-        fh.writelines('v %.9g %.9g %.9g\n' % tuple(r) for r in v.tolist())
+        if c is not None:
+            fh.writelines('v %.9g %.9g %.9g %.9g %.9g %.9g\n' % tuple(r) for r in np.concatenate([v, c], 1).tolist())
+        else:
+            fh.writelines('v %.9g %.9g %.9g\n' % tuple(r) for r in v.tolist())
         if n is not None:
             fh.writelines('vn %.9g %.9g %.9g\n' % tuple(r) for r in n.tolist())
             fh.writelines('f %d//%d %d//%d %d//%d\n' % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
@@ -160,12 +213,13 @@ def save_obj(fn, vertices, faces, normals=None):
     return fn
 
 
-def load_mesh_indexed(mesh_fn):
-    """(V, 3) float32 vertices and (T, 3) faces; the plugin is chosen the way the reference does (mesh_to_sdf.py:12)."""
-    v, f = load_obj(mesh_fn) if mesh_fn.endswith('.obj') else load_ply(mesh_fn)
+def load_mesh_indexed(mesh_fn, colors=False):
+    """(V, 3) float32 vertices and (T, 3) faces; the plugin is chosen the way the reference does (mesh_to_sdf.py:12).  colors: a third
+    element, the (V, 3) float32 vertex colours of the file, or None when it has none."""
+    v, f, c = load_obj(mesh_fn, True) if mesh_fn.endswith('.obj') else load_ply(mesh_fn, True)
     if len(f) == 0:
         raise ValueError(f'{mesh_fn}: no faces')
-    return v, f
+    return (v, f, c) if colors else (v, f)
 
 
 def load_mesh(mesh_fn):

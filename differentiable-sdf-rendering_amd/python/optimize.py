@@ -4,7 +4,8 @@
 Same flags as the reference (argparse prefix matching keeps `--optconfig` working); `--llvm` is
 accepted and ignored (there is one backend: HIP on the MI355X).  Reference images come from the
 scene's target SDF (scenes.py) rendered with the method's integrator at `--refspp`; with `--meshrefs` a scene that has a mesh
-renders them from the mesh itself, like the reference does (dsdf.mesh_render)."""
+renders them from the mesh itself, like the reference does (dsdf.mesh_render) -- with the vertex colours of the mesh file as the
+diffuse reflectance when it carries some."""
 import argparse
 import os
 import sys
@@ -37,7 +38,8 @@ def render_reference_images(scene_config, config, ref_spp=1024, force=False, ver
     folder = join(RENDER_DIR, scene_config.scene, scene_config.name, config.integrator, 'ref')
     os.makedirs(folder, exist_ok=True)
     scene = None
-    mesh = load_target_mesh(scene_config.scene) if mesh_refs else None
+    mesh = load_target_mesh(scene_config.scene, colors=True) if mesh_refs else None      # (triangles, normals, corner colours or None)
+    mesh_has_colors = mesh is not None and mesh[2] is not None
     if mesh_refs and mesh is None:
         print(f"[optimize] --meshrefs: scene '{scene_config.scene}' has no mesh; reference images come from its target SDF")
     for idx, sensor in enumerate(scene_config.sensors):
@@ -53,7 +55,8 @@ def render_reference_images(scene_config, config, ref_spp=1024, force=False, ver
             if config.integrator == 'sdf_direct_reparam':
                 if any(k.endswith('roughness.volume.data') for k in scene_config.param_keys):
                     props['roughness'] = 0.4
-                props['reflectance'] = load_target_albedo(scene_config.scene)
+                if not mesh_has_colors:
+                    props['reflectance'] = load_target_albedo(scene_config.scene)       # (no colours in the file: the stand-in volume)
             with torch.no_grad():
                 mesh, img = _render_mesh_reference(mesh, config.integrator, props, sensor, idx + 41, spp)
             write_image(fn, img)

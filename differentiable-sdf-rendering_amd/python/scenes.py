@@ -61,18 +61,22 @@ def load_target_sdf(scene_name, res=128, device='cuda'):
     return _blobs(res, seed, device)
 
 
-def load_target_mesh(scene_name, smooth=True, device='cuda'):
+def load_target_mesh(scene_name, smooth=True, device='cuda', colors=False):
     """The scene's mesh itself, for reference images rendered from it (dsdf.mesh_render): (triangles, normals), both (T,3,3) float32
     on `device`, shifted by +0.5 from the readers' [-0.5, 0.5]^3 into the SDF's unit cube (the sensors look at (0.5, 0.5, 0.5)) -- or
-    None when the scene has no mesh.  smooth: angle-weighted vertex normals (Mitsuba's for a file without normals), else face normals."""
+    None when the scene has no mesh.  smooth: angle-weighted vertex normals (Mitsuba's for a file without normals), else face normals.
+    colors: a third element, the file's vertex colours at the triangle corners (T,3,3) -- what dsdf.MeshBvh(colors=) takes -- or None
+    when the file has none."""
     for ext in ('.obj', '.ply'):
         mesh = os.path.join(SCENE_DIR, scene_name, scene_name + ext)
         if os.path.isfile(mesh):
             import mesh_to_sdf
-            v, f = mesh_to_sdf.load_mesh_indexed(mesh)
+            v, f, c = mesh_to_sdf.load_mesh_indexed(mesh, colors=True)
             tri = torch.as_tensor(v[f] + np.float32(0.5), dtype=torch.float32, device=device).contiguous()
             nrm = torch.as_tensor(mesh_to_sdf.vertex_normals(v, f, smooth), dtype=torch.float32, device=device).contiguous()
-            return tri, nrm
+            if not colors:
+                return tri, nrm
+            return tri, nrm, (None if c is None else torch.as_tensor(c[f], dtype=torch.float32, device=device).contiguous())
     return None
 
 

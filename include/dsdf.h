@@ -464,6 +464,15 @@ int dsdf_mesh_render_forward(const float *bvh, const dsdf_params *prm, const dsd
                              const float *offsets, const uint32_t *seeds, int integrator, const dsdf_shading *shading, float *image_out,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* dsdf_mesh_render_forward with a reflectance per triangle corner: corner_colors n_triangles x 9 (rgb of p0, p1, p2; linear reflectance),
+ * indexed by the ORIGINAL triangle index (the caller's order, whatever permutation the buffer was built with).  DSDF_DIRECT takes the
+ * reflectance of a hit as (1 - u - v) c0 + u c1 + v c2 in place of the lookup in shading->albedo, which may then be NULL and is not read;
+ * `shading` itself (->env_radiance, ->hide_emitters, ->emitter_samples; bsdf = 0, use_mis = 0) is still required.  The other two integrators
+ * ignore the colours.  corner_colors = NULL: exactly dsdf_mesh_render_forward.  Error texts carry that call's name. */
+int dsdf_mesh_render_forward_colors(const float *bvh, const float *corner_colors, const dsdf_params *prm, const dsdf_camera *cams, int n_views,
+                                    int width, int height, int spp, const float *offsets, const uint32_t *seeds, int integrator,
+                                    const dsdf_shading *shading, float *image_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- triangle mesh of the rendered surface: the level set {f = iso} of the tricubic lookup f of dsdf_eval_cubic (csrc/dsdf_iso.h) ----
  * Marching tetrahedra on a lattice of nx x ny x nz cells over the unit cube of the grid, IN THE CUBE'S OWN FRAME: `sdf.p` and a grid
  * transform play no part in these four calls, in either build of the library (the caller maps the result out).
@@ -490,6 +499,12 @@ int dsdf_iso_emit(const float *values, int nx, int ny, int nz, float iso, const 
 int dsdf_iso_refine(const float *padded, int rx, int ry, int rz, const float *values, int nx, int ny, int nz, float iso,
                     const int32_t *vert_edge, int64_t n_vert, int steps, float *positions /* V x 3 */, float *normals /* V x 3 or NULL */,
                     void *stream);
+
+/* Trilinear lookup of a (vz, vy, vx, channels) fp32 volume on the unit cube, channels 1 or 3, at n points (n x 3, in the volume's frame):
+ * out n x channels.  The value the direct integrator reads there (shading->albedo, ->roughness): texel centres (i + 0.5) / res, clamped
+ * indices.  Bakes a reflectance volume onto the vertices of an extracted mesh (their WORLD-space positions: the volume lives in world
+ * space).  n = 0 returns DSDF_OK without a launch. */
+int dsdf_volume_sample(const float *volume, int vx, int vy, int vz, int channels, const float *points, int64_t n, float *out, void *stream);
 
 #ifdef __cplusplus
 }

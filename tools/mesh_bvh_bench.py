@@ -5,7 +5,7 @@
   - 1 M random rays and 1 M camera rays against each, through the BVH and through the brute-force kernel (dsdf.mesh_raycast), with
     the results compared bit for bit;
   - `mesh_to_sdf.create_sdf` at 64^3 both ways (20 k triangles);
-  - one 512^2, 64-spp mesh render per integrator (20 k triangles);
+  - one 512^2, 64-spp mesh render per integrator (20 k triangles), and the direct one again with corner colours;
   - with `--build-lds` (run where hipcc is; no GPU needed) a second library that stages the top 255 nodes of the tree in LDS
     (-DDSDF_BVH_LDS_NODES=255) is compiled to lib/variants/libdsdf_bvh_lds.so; when that file exists the ray casts are also timed
     through it, alternating with the default build (no staging).
@@ -126,6 +126,10 @@ def main():
             for integ in ('sdf_silhouette_reparam', 'sdf_simple_shading_reparam', 'sdf_direct_reparam'):
                 res[f'render512_spp64_{integ}_ms'] = timed(lambda: dsdf.mesh_render(rb, [sen], 64, seeds=[3], integrator=integ,
                                                                                    shading=sh if 'direct' in integ else None), a.reps)
+            # the same render with a reflectance per triangle corner (the volume's value at the corners) instead of the volume lookup
+            cb = dsdf.MeshBvh(tri_u, nrm, colors=dsdf.sample_volume(sh.albedo, tri_u.reshape(-1, 3)).reshape(-1, 3, 3))
+            res['render512_spp64_sdf_direct_reparam_colors_ms'] = timed(lambda: dsdf.mesh_render(cb, [sen], 64, seeds=[3], integrator='sdf_direct_reparam',
+                                                                                              shading=dsdf.Shading(None, 1.0)), a.reps)
             print(json.dumps({k: v_ for k, v_ in res.items() if k.startswith(('create', 'render'))}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
