@@ -24,6 +24,10 @@
 // triangle's edge at 80 k triangles on a sphere).  A triangle whose corners are (nearly) collinear has a determinant that is
 // rounding noise for EVERY ray -- the loop over all triangles can accept it anywhere -- so it gets an infinite box and is
 // always tested.  The window test is closed (near <= best): a triangle at exactly the best distance with a lower index wins.
+//
+// CLOSEST-POINT queries (tri_closest, box_dist2, bvh_closest) descend the same tree by the distance of the query point to the boxes
+// and keep the same promise towards tri_closest: the bits of the loop over all triangles, for query points within roughly 100
+// extents of the mesh -- the same margin against the roundings of a squared distance; the argument stands at bvh_closest.
 #pragma once
 #include <string.h>
 #include "dsdf_math.h"
@@ -274,6 +278,150 @@ DSDF_HD bool bvh_traverse(const BvhView &B, const Nodes &N, V3 o, V3 d, float t_
     }
 }
 
+// ---- closest point -------------------------------------------------------------------------------------------------------
+// The point of the triangle p[0..8] = p0 p1 p2 nearest to x, as q = p0 + u e1 + v e2 with u, v >= 0, u + v <= 1, and d2 = |x - q|^2.
+// The minimum is attained in the face, on an edge or at a corner; instead of deciding the region first, every candidate is
+// evaluated and the nearest kept: the clamped foot on each of the three edges (a corner is a clamped foot) and, when it falls
+// inside, the foot in the plane.  d2 is ALWAYS |x - (p0 + u e1 + v e2)|^2 of the (u, v) kept, the distance to an actual point of the
+// triangle -- so a candidate that rounding admits or refuses wrongly costs the difference between two nearly equal distances,
+// never a wrong one, and a degenerate triangle needs no threshold: collinear corners have no plane (nn == 0, or a foot that is
+// not finite or not inside) and leave the three edges, whose union is the longest one; three equal corners leave p0.  No division
+// sees a zero: an edge parameter divides only when 0 < w . e < e . e, the plane foot only when nn > 0.
+// Every product and sum is rounded on its own, for the reason given at tri_intersect: k_mesh_closest, the traversal and the host
+// build must compute the same bits.  A NaN in x makes every d2 NaN, which no comparison of the callers accepts.
+struct TriClosest { float d2, u, v; };
+DSDF_HD float edge_param(V3 e, V3 w) {           // the foot of w on the segment 0 .. e, as a fraction of e; a zero edge is its start
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float we = dot_unfused(w, e), ee = dot_unfused(e, e);
+    if (!(we > 0.f)) return 0.f;
+    if (we >= ee) return 1.f;
+    return we / ee;
+}
+DSDF_HD void tri_closest_try(V3 e1, V3 e2, V3 w, float u, float v, bool first, TriClosest &c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const V3 r = mk(w.x - (u * e1.x + v * e2.x), w.y - (u * e1.y + v * e2.y), w.z - (u * e1.z + v * e2.z));
+    const float d2 = dot_unfused(r, r);
+    if (first || d2 < c.d2) { c.d2 = d2; c.u = u; c.v = v; }
+}
+DSDF_HD void tri_closest(const float *p, V3 x, TriClosest &c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const V3 e1 = mk(p[3] - p[0], p[4] - p[1], p[5] - p[2]), e2 = mk(p[6] - p[0], p[7] - p[1], p[8] - p[2]);
+    const V3 w = mk(x.x - p[0], x.y - p[1], x.z - p[2]);
+    tri_closest_try(e1, e2, w, edge_param(e1, w), 0.f, true, c);                          // p0 p1
+    tri_closest_try(e1, e2, w, 0.f, edge_param(e2, w), false, c);                         // p0 p2
+    const float s = edge_param(mk(e2.x - e1.x, e2.y - e1.y, e2.z - e1.z), mk(w.x - e1.x, w.y - e1.y, w.z - e1.z));
+    tri_closest_try(e1, e2, w, 1.f - s, s, false, c);                                     // p1 p2
+    const V3 n = mk(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+    const float nn = dot_unfused(n, n);
+    if (nn > 0.f) {
+        const V3 a = mk(w.y * e2.z - w.z * e2.y, w.z * e2.x - w.x * e2.z, w.x * e2.y - w.y * e2.x);      // w x e2
+        const V3 b = mk(e1.y * w.z - e1.z * w.y, e1.z * w.x - e1.x * w.z, e1.x * w.y - e1.y * w.x);      // e1 x w
+        const float u = dot_unfused(a, n) / nn, v = dot_unfused(b, n) / nn;
+        if (u >= 0.f && v >= 0.f && u + v <= 1.f) tri_closest_try(e1, e2, w, u, v, false, c);
+    }
+}
+// q = p0 + u e1 + v e2, rounded the same way everywhere
+DSDF_HD V3 tri_point(const float *p, float u, float v) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return mk(p[0] + (u * (p[3] - p[0]) + v * (p[6] - p[0])), p[1] + (u * (p[4] - p[1]) + v * (p[7] - p[1])),
+              p[2] + (u * (p[5] - p[2]) + v * (p[8] - p[2])));
+}
+
+// Squared distance of x to the box b = lo.xyz hi.xyz: the sum over the axes of max(lo - x, 0, x - hi)^2.  From the layout: the
+// inverted box of an empty leaf (lo = +inf, hi = -inf) gives max(+inf, 0, +inf)^2 = +inf, which bvh_closest never enters; the
+// infinite box of a (nearly) collinear triangle (lo = -inf, hi = +inf) gives max(-inf, 0, -inf)^2 = 0 and is always entered.
+// (fmaxf drops a NaN operand: a NaN query is at distance 0 of every box, visits every leaf and accepts nothing.)
+DSDF_HD float box_dist2(const float *b, V3 x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float dx = fmaxf(fmaxf(b[0] - x.x, 0.f), x.x - b[3]), dy = fmaxf(fmaxf(b[1] - x.y, 0.f), x.y - b[4]),
+                dz = fmaxf(fmaxf(b[2] - x.z, 0.f), x.z - b[5]);
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// CONSERVATIVE towards tri_closest, as the ray boxes are towards tri_intersect: the traversal must return bit for bit what the
+// loop over all triangles returns, so the fp32 box_dist2 of a box must not exceed the fp32 d2 of any triangle inside it.  In
+// exact arithmetic the distance to a box is at most the distance to anything inside; the leaf boxes are grown by the margin
+// m = 2^-13 ext on every side, which takes at least g m off the squared distance on an axis where the point is a gap g > m away
+// (and a point within m of the box on every axis is at distance 0): about 1e-4 ext d for a point at distance d.  Against that
+// stand the roundings: d2 is a sum of squares of differences of coordinates of size R = |x| + ext, each off by ~1e-7 R, so d2 is
+// off by ~1e-7 (d^2 + d R), on either side.  The margin covers it while 1e-4 ext > ~1e-6 d, i.e. for query points within roughly
+// 100 extents of the mesh; the tests stay inside 10.  Beyond that range the result is still the distance to some triangle, only
+// not necessarily the bits of the loop.
+struct BvhClosest { float d2; int prim, slot; float u, v; };        // prim: original triangle index, -1 = none within max_d2
+// closed at the starting bound, and on equal d2 the lower original index wins: what `<` gives a loop in index order
+DSDF_HD void closest_update(BvhClosest &r, const TriClosest &c, int idx, int s) {
+    if ((c.d2 < r.d2 || (c.d2 == r.d2 && (r.prim < 0 || idx < r.prim))) && c.d2 < INFINITY) { r.d2 = c.d2; r.prim = idx; r.slot = s; r.u = c.u; r.v = c.v; }
+}
+DSDF_HD void bvh_closest_leaf(const BvhView &B, int j, V3 x, BvhClosest &r) {
+    for (int k = 0; k < DSDF_BVH_LEAF; ++k) {
+        const int s = DSDF_BVH_LEAF * j + k;
+        float p[DSDF_BVH_SLOT];
+        bvh_load_slot(B, s, p);
+        const int idx = f2i(p[9]);
+        if (idx < 0) break;                      // (slots fill from the left)
+        TriClosest c;
+        tri_closest(p, x, c);
+        closest_update(r, c, idx, s);
+    }
+}
+// The descent of bvh_traverse -- the nearer child first, one owed bit per level, a pop by heap arithmetic: three registers of state
+// -- as a second loop, so that the ray path compiles to what it did.  A box is entered when box_dist2 <= r.d2 (closed: a triangle
+// at exactly the best distance with a lower index still wins) and finite.
+template <class Nodes>
+DSDF_HD void bvh_closest(const BvhView &B, const Nodes &N, V3 x, float max_d2, BvhClosest &r) {
+    r.d2 = max_d2; r.prim = -1; r.slot = 0; r.u = 0.f; r.v = 0.f;
+    const uint32_t inner = (uint32_t)B.L - 1u;
+    if (inner == 0u) { bvh_closest_leaf(B, 0, x, r); return; }
+    uint32_t i = 0;
+    int depth = 0;
+    uint64_t owed = 0;
+    for (;;) {
+        float nd[12];
+        N.load(i, nd);
+        const float n0 = box_dist2(nd, x), n1 = box_dist2(nd + 6, x);
+        const bool h0 = n0 <= r.d2 && n0 < INFINITY, h1 = n1 <= r.d2 && n1 < INFINITY;
+        bool down = h0 || h1;
+        if (down) {
+            if (h0 && h1) owed |= (uint64_t)1 << depth;
+            i = 2u * i + 1u + ((h1 && (!h0 || n1 < n0)) ? 1u : 0u);
+            ++depth;
+        }
+        for (;;) {
+            if (down) {
+                if (i < inner) break;
+                bvh_closest_leaf(B, (int)(i - inner), x, r);
+            }
+            const uint64_t m = owed & (((uint64_t)1 << depth) - 1u);
+            if (m == 0) return;
+            const int k = 63 - __builtin_clzll(m);
+            owed &= ~((uint64_t)1 << k);
+            const uint32_t a = ((i + 1u) >> (depth - k - 1)) - 1u;
+            i = ((a - 1u) ^ 1u) + 1u;
+            depth = k + 1;
+            down = true;
+        }
+    }
+}
+// The bound the searches start from, and the result they report, for a limit on the DISTANCE: sqrtf is monotone, so every d2 with
+// sqrtf(d2) <= max_dist lies below max_dist^2 widened by a few ulps; closest_dist then applies the limit itself, closed.
+DSDF_HD float closest_bound(float max_dist) { return max_dist * max_dist * (1.f + 4.76837158203125e-7f); }
+DSDF_HD float closest_dist(BvhClosest &r, float max_dist) {
+    const float d = sqrtf(r.d2);
+    if (r.prim >= 0 && d <= max_dist) return d;
+    r.prim = -1;
+    return INFINITY;
+}
+
 // the shading normal of a hit: the interpolated vertex normals when the buffer has them, else the geometric normal
 DSDF_HD V3 bvh_normal(const BvhView &B, const BvhHit &h) {
     V3 n;
@@ -358,6 +506,36 @@ __global__ __launch_bounds__(256) void k_mesh_bvh_raycast(const float *__restric
     t_out[i] = h.t;
     if (back_out) back_out[i] = (h.prim >= 0 && h.det < 0.f) ? 1 : 0;
     if (prim_out) prim_out[i] = h.prim;
+}
+
+// what both closest-point kernels write for point i from the search result and the nine floats of the winning triangle
+__device__ __forceinline__ void closest_store(BvhClosest r, const float *p, float max_dist, int64_t i, float *__restrict__ dist_out,
+                                              int32_t *__restrict__ prim_out, float *__restrict__ point_out, float *__restrict__ bary_out) {
+    dist_out[i] = closest_dist(r, max_dist);
+    if (prim_out) prim_out[i] = r.prim;
+    const bool found = r.prim >= 0;
+    if (point_out) {
+        const V3 q = found ? tri_point(p, r.u, r.v) : mk(0.f, 0.f, 0.f);
+        point_out[3 * i] = q.x; point_out[3 * i + 1] = q.y; point_out[3 * i + 2] = q.z;
+    }
+    if (bary_out) { bary_out[2 * i] = found ? r.u : 0.f; bary_out[2 * i + 1] = found ? r.v : 0.f; }
+}
+
+// one lane per query point
+__global__ __launch_bounds__(256) void k_mesh_bvh_closest(const float *__restrict__ bvh, const float *__restrict__ pts, int64_t n, float max_dist,
+                                                          float *__restrict__ dist_out, int32_t *__restrict__ prim_out,
+                                                          float *__restrict__ point_out, float *__restrict__ bary_out) {
+    __shared__ float4 top[DSDF_BVH_LDS_FLOAT4];
+    const BvhView B = bvh_view(bvh);
+    const StagedNodes N = stage_nodes(B, top);
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const V3 x = mk(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+    BvhClosest r;
+    bvh_closest(B, N, x, closest_bound(max_dist), r);
+    float p[DSDF_BVH_SLOT];
+    bvh_load_slot(B, r.slot, p);                    // (slot 0 exists in every buffer)
+    closest_store(r, p, max_dist, i, dist_out, prim_out, point_out, bary_out);
 }
 
 // ---- build ---------------------------------------------------------------------------------------------------------------
@@ -490,6 +668,14 @@ int dsdf_mesh_bvh_raycast(const float *bvh, const float *rays_o, const float *ra
     if (!bvh || !rays_o || !rays_d || !t_out || n < 0) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_raycast: bad argument");
     return launch("k_mesh_bvh_raycast", k_mesh_bvh_raycast, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, bvh, rays_o,
                   rays_d, n, t_min, t_out, backface_out, prim_out);
+}
+
+int dsdf_mesh_bvh_closest(const float *bvh, const float *points, int64_t n, float max_dist, float *dist_out, int32_t *prim_out,
+                          float *point_out, float *bary_out, void *stream) {
+    if (n == 0) return DSDF_OK;
+    if (!bvh || !points || !dist_out || n < 0 || !(max_dist >= 0.f)) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_closest: bad argument");
+    return launch("k_mesh_bvh_closest", k_mesh_bvh_closest, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, bvh, points, n,
+                  max_dist, dist_out, prim_out, point_out, bary_out);
 }
 
 size_t dsdf_mesh_render_workspace_size(int width, int height, int n_views) {

@@ -30,6 +30,7 @@
 //   k_forward_tangent          forward mode: the same queue, tangent film
 //   k_redist_*, k_mesh_raycast redistancing, mesh ray caster                              [dsdf_redistance.h, dsdf_mesh.h]
 //   k_mesh_morton, k_bvh_*, k_mesh_bvh_raycast, k_mesh_render<NCH>   mesh BVH: build, stackless traversal, primal render of a mesh   [dsdf_bvh.h]
+//   k_mesh_closest, k_mesh_bvh_closest   closest point of a mesh: brute force and through the BVH             [dsdf_mesh.h, dsdf_bvh.h]
 //
 // wave = 64 lanes; one lane = one film sample, consecutive lanes = consecutive
 // samples of the same pixel (reference lane order, reparam.py:140-155), so for

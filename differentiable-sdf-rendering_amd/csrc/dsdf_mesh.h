@@ -44,3 +44,44 @@ extern "C" int dsdf_mesh_raycast(const float *triangles, int n_triangles, const 
                        rays_d, n, t_min, t_out, backface_out);
     return check_launch("k_mesh_raycast");
 }
+
+// ---- closest point -------------------------------------------------------------------------------------------------------
+// The same shape for closest-point queries (tri_closest, dsdf_bvh.h): every thread tests its point against the staged triangles,
+// in index order, so `closest_update` keeps the lowest index among equal distances.  It serves small meshes, and on the device it
+// is the yardstick of the traversal (k_mesh_bvh_closest returns the same bits).
+__global__ __launch_bounds__(256) void k_mesh_closest(const float *__restrict__ tri, int n_tri, const float *__restrict__ pts, int64_t n,
+                                                      float max_dist, float *__restrict__ dist_out, int32_t *__restrict__ prim_out,
+                                                      float *__restrict__ point_out, float *__restrict__ bary_out) {
+    __shared__ float tile[DSDF_MESH_TILE * 9];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = i < n;
+    V3 x = mk(0.f, 0.f, 0.f);
+    if (on) x = mk(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+    BvhClosest r;
+    r.d2 = closest_bound(max_dist); r.prim = -1; r.slot = 0; r.u = 0.f; r.v = 0.f;
+    for (int t0 = 0; t0 < n_tri; t0 += DSDF_MESH_TILE) {
+        const int cnt = min(DSDF_MESH_TILE, n_tri - t0);
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt * 9; e += blockDim.x) tile[e] = tri[(size_t)t0 * 9 + e];
+        __syncthreads();
+        for (int k = 0; k < cnt; ++k) {
+            TriClosest c;
+            tri_closest(tile + k * 9, x, c);
+            closest_update(r, c, t0 + k, 0);
+        }
+    }
+    if (!on) return;
+    float p[9];
+    const float *src = tri + (size_t)9 * (r.prim >= 0 ? r.prim : 0);
+    for (int e = 0; e < 9; ++e) p[e] = src[e];
+    closest_store(r, p, max_dist, i, dist_out, prim_out, point_out, bary_out);
+}
+
+extern "C" int dsdf_mesh_closest(const float *triangles, int n_triangles, const float *points, int64_t n, float max_dist, float *dist_out,
+                                 int32_t *prim_out, float *point_out, float *bary_out, void *stream) {
+    if (n == 0) return DSDF_OK;
+    if (!triangles || n_triangles < 1 || !points || !dist_out || n < 0 || !(max_dist >= 0.f))
+        return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_closest: bad argument");
+    return launch("k_mesh_closest", k_mesh_closest, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, triangles, n_triangles,
+                  points, n, max_dist, dist_out, prim_out, point_out, bary_out);
+}

@@ -864,6 +864,7 @@ class MeshBvh:
             if self.colors.device != tri.device:
                 raise _lib.DsdfError("colors must live on the device of the triangles")
         self.device, self.n_triangles, self.has_normals = tri.device, T, nrm is not None
+        self.triangles = tri.reshape(T, 3, 3)        # (the caller's order: what mesh_distance samples)
         self.buffer = torch.empty(int(lib.dsdf_mesh_bvh_size(T, int(nrm is not None))), dtype=torch.float32, device=tri.device)
         codes = torch.empty(T, dtype=torch.int32, device=tri.device)
         with torch.cuda.device(tri.device):
@@ -884,6 +885,93 @@ class MeshBvh:
             _lib.check(lib.dsdf_mesh_bvh_raycast(_ptr(self.buffer), _ptr(rays_o), _ptr(rays_d), n, C.c_float(t_min), _ptr(t), _ptr(back),
                                                  _ptr(prim), _stream()))
         return (t, back, prim) if return_prim else (t, back)
+
+    def closest(self, points, max_dist=float('inf'), return_prim=False, return_point=False, return_bary=False):
+        """mesh_closest through the hierarchy (dsdf_mesh_bvh_closest): the same arguments, bit for bit the brute-force result."""
+        return _closest(lambda lib, *a: lib.dsdf_mesh_bvh_closest(_ptr(self.buffer), *a), self.device, points, max_dist, return_prim,
+                        return_point, return_bary)
+
+
+def _closest(entry, device, points, max_dist, return_prim, return_point, return_bary):
+    lib = _lib.load()
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.DsdfError(f"points must be (N,3), got {tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    pts = _require_dev(points, 'points')
+    if pts.device != device:
+        raise _lib.DsdfError("points must live on the device of the mesh")
+    n = int(pts.shape[0])
+    dist = torch.empty(n, dtype=torch.float32, device=device)
+    prim = torch.empty(n, dtype=torch.int32, device=device) if return_prim else None
+    point = torch.empty(n, 3, dtype=torch.float32, device=device) if return_point else None
+    bary = torch.empty(n, 2, dtype=torch.float32, device=device) if return_bary else None
+    with torch.cuda.device(device):
+        _lib.check(entry(lib, _ptr(pts), n, C.c_float(max_dist), _ptr(dist), _ptr(prim), _ptr(point), _ptr(bary), _stream()))
+    out = (dist,) + tuple(t for t in (prim, point, bary) if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def mesh_closest(triangles, points, max_dist=float('inf'), return_prim=False, return_point=False, return_bary=False):
+    """Closest point of a triangle soup (T,3,3) to each of `points` (N,3), every point against every triangle (dsdf_mesh_closest; small
+    meshes -- MeshBvh.closest serves large ones with the same bits) -> dist (N,), +inf where no triangle lies within max_dist (closed), or a
+    tuple with, in this order, prim (N,) int32: the index of the closest triangle (-1: none; the lower one on equal distance), point (N,3):
+    the closest point p0 + u e1 + v e2, bary (N,2): (u, v).  Exact for degenerate triangles too."""
+    tri = _require_dev(triangles.reshape(-1, 9), 'triangles')
+    if tri.shape[0] < 1:
+        raise _lib.DsdfError("mesh_closest needs at least one triangle")
+    return _closest(lambda lib, *a: lib.dsdf_mesh_closest(_ptr(tri), int(tri.shape[0]), *a), tri.device, points, max_dist, return_prim,
+                    return_point, return_bary)
+
+
+def sample_surface(triangles, n, seed=0):
+    """`n` points uniform on the surface of a triangle soup (T,3,3) -> (points (n,3), prim (n,) int64, bary (n,2)): a triangle is drawn
+    in proportion to its area (searchsorted on the cumulative areas, fp64), the point inside it by the square-root warp
+    (u, v) = (sqrt(r1) (1 - r2), sqrt(r1) r2), point = p0 + u e1 + v e2.  Deterministic for a seed on a device.  Torch plumbing, no kernel.
+    A triangle without area is never drawn; a mesh without area raises DsdfError."""
+    tri = _require_dev(triangles.reshape(-1, 3, 3), 'triangles')
+    dev = tri.device
+    t64 = tri.double()
+    e1, e2 = t64[:, 1] - t64[:, 0], t64[:, 2] - t64[:, 0]
+    area = 0.5 * torch.linalg.norm(torch.linalg.cross(e1, e2), dim=1)
+    cum = torch.cumsum(area, 0)
+    total = float(cum[-1]) if cum.numel() else 0.0
+    if not (total > 0.0 and total < float('inf')):
+        raise _lib.DsdfError(f"sample_surface: the mesh has no surface to sample (total area {total})")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    r = torch.rand(int(n), 3, dtype=torch.float64, device=dev, generator=gen)
+    # right=True: the first triangle whose cumulative area EXCEEDS the draw, so one that adds nothing is never the answer
+    prim = torch.searchsorted(cum, r[:, 0] * total, right=True).clamp_(max=int(torch.nonzero(area > 0)[-1]))
+    s = torch.sqrt(r[:, 1])
+    u, v = s * (1.0 - r[:, 2]), s * r[:, 2]
+    pts = t64[prim, 0] + u[:, None] * e1[prim] + v[:, None] * e2[prim]
+    return pts.float().contiguous(), prim, torch.stack([u, v], -1).float()
+
+
+def mesh_distance(a, b, n=200_000, seed=0, threshold=None):
+    """How far two surfaces are apart.  `a`, `b`: (T,3,3) triangles or MeshBvh objects (sampled from their `.triangles`).
+    `n` points are sampled on each (sample_surface; seeds `seed` and `seed + 1`) and queried against the other mesh through its BVH ->
+    a dict: a_to_b_mean / b_to_a_mean / a_to_b_max / b_to_a_max, chamfer_l1 = (a_to_b_mean + b_to_a_mean) / 2, chamfer_l2 = mean(d_ab^2) +
+    mean(d_ba^2), hausdorff = the larger maximum (of the SAMPLED points: a lower bound of the true one); with `threshold`: precision and
+    recall = the shares of d_ab and d_ba that are <= threshold, fscore = their harmonic mean (0 when both are 0); and the raw points_a,
+    points_b, dist_a_to_b, dist_b_to_a (device tensors).  The statistics are accumulated in fp64."""
+    def mesh(m, name):
+        if isinstance(m, MeshBvh):
+            return m.triangles, m
+        tri = _require_dev(m.reshape(-1, 3, 3), name)
+        return tri, MeshBvh(tri)
+    (ta, ba), (tb, bb) = mesh(a, 'a'), mesh(b, 'b')
+    pa, pb = sample_surface(ta, n, seed)[0], sample_surface(tb, n, int(seed) + 1)[0]
+    dab, dba = bb.closest(pa), ba.closest(pb)
+    d1, d2 = dab.double(), dba.double()
+    out = {'a_to_b_mean': float(d1.mean()), 'b_to_a_mean': float(d2.mean()), 'a_to_b_max': float(d1.max()), 'b_to_a_max': float(d2.max())}
+    out['chamfer_l1'] = (out['a_to_b_mean'] + out['b_to_a_mean']) / 2
+    out['chamfer_l2'] = float((d1 * d1).mean()) + float((d2 * d2).mean())
+    out['hausdorff'] = max(out['a_to_b_max'], out['b_to_a_max'])
+    if threshold is not None:
+        p, r = float((d1 <= float(threshold)).double().mean()), float((d2 <= float(threshold)).double().mean())
+        out.update(precision=p, recall=r, fscore=2 * p * r / (p + r) if p + r > 0 else 0.0)
+    out.update(points_a=pa, points_b=pb, dist_a_to_b=dab, dist_b_to_a=dba)
+    return out
 
 
 def mesh_render(bvh, sensors, spp, seeds=None, offsets=None, integrator=DSDF_SILHOUETTE, shading=None, emitter_samples=None,

@@ -452,6 +452,17 @@ int dsdf_mesh_bvh_build(const float *triangles, const float *normals, const int3
 int dsdf_mesh_bvh_raycast(const float *bvh, const float *rays_o, const float *rays_d, int64_t n, float t_min, float *t_out,
                           int32_t *backface_out, int32_t *prim_out, void *stream);
 
+/* Closest point of a triangle soup to each of n points (n x 3), by brute force (small meshes; the yardstick of the call below) and
+ * through the BVH: the same bits.  max_dist >= 0 limits the search (closed; INFINITY: no limit).  dist_out n: the distance (+inf: no
+ * triangle within max_dist); prim_out n (optional, int32): the ORIGINAL index of the closest triangle, -1 for none, on equal distance
+ * the lower index; point_out n x 3 (optional): the closest point p0 + u e1 + v e2 (0 for none); bary_out n x 2 (optional): (u, v), with
+ * u, v >= 0 and u + v <= 1.  Exact for every finite triangle, degenerate ones included (collinear corners: their longest segment).
+ * The two calls agree bit for bit for points within ~100 extents of the mesh (csrc/dsdf_bvh.h).  n = 0 returns DSDF_OK without a launch. */
+int dsdf_mesh_closest(const float *triangles, int n_triangles, const float *points, int64_t n, float max_dist,
+                      float *dist_out, int32_t *prim_out, float *point_out, float *bary_out, void *stream);
+int dsdf_mesh_bvh_closest(const float *bvh, const float *points, int64_t n, float max_dist,
+                          float *dist_out, int32_t *prim_out, float *point_out, float *bary_out, void *stream);
+
 /* Primal render of the mesh: dsdf_render_forward with the intersection routine swapped -- same lane order, sampler rules (offsets /
  * seeds), camera ray, film block, re-projection and develop; no reparameterisation (det = 1).  Per sample: DSDF_SILHOUETTE [hit];
  * DSDF_SIMPLE_SHADING max(n . prm->light_dir, 0); DSDF_DIRECT the emitter-sampling statement of sdf_direct_reparam.py:29-75 with the
