@@ -1481,7 +1481,7 @@ static int pixel_proof(const PassCtx &c, const Workspace &ws, const dsdf_camera 
                      min_bounds(c.padded, c.rx, c.ry, c.rz, level), max_bounds(c.padded, c.rx, c.ry, c.rz), c.pp, VB, dst, M.step0, M.step, hstep, und, list_g, plane)))
         return rc;
     if (und && (rc = launch("k_pixel_hit_fine", k_pixel_hit_fine, dim3((unsigned)((npix * nv + 255) / 256)), blk, st, device_view(c),
-                            fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), vb, c.pp, VB, dst, plane, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))
+                            min_bounds(c.padded, c.rx, c.ry, c.rz, 0), M.cstep, fmin, fine_bounds(c.padded, c.rx, c.ry, c.rz), vb, c.pp, VB, dst, plane, und, und + DSDF_UNDECIDED_HDR, fstep, (int)want_hit)))
         return rc;
     if ((rc = launch("k_skip_dilate", k_skip_dilate, pgrid, blk, st, VB, dst, plane))) return rc;
     if (dst == sh.buf) {

@@ -228,6 +228,57 @@ DSDF_HD ValueMargin value_margin(const ValueBound &vb) {
     return m;
 }
 
+// ---- Where on its centre ray a listed pixel's fine stages have anything to find.
+// The fine stages read, at every sample position, the window bounds of the B-spline cell c = floor(X - 0.5) the position X (voxels)
+// lies in: taps [c + DSDF_FINE_LO, c + DSDF_FINE_HI] per axis, all of them integers in (X - 3.5, X + 2.5].  The dilated minima of the
+// 8^3 level (min_bounds(0): blocks of C = 8 voxels, dilated by one block) bound, at a point Y of block b = floor(Y) >> 3, every tap of
+// [8b - 8, 8b + 15], which contains every integer of [Y - C, Y + C - 1].  So a coarse sample at Y whose bound exceeds a threshold
+// certifies that the window MINIMUM -- and with it the window maximum and every spline value -- of every position X with
+// |X - Y| <= C - 3.5 = 4.5 voxels per axis exceeds it too  (X + 2.5 <= Y + 7, X - 3.5 >= Y - 8;  clamping taps and blocks to the grid
+// is monotone, so the containment survives it).  Both X and Y lie ON the centre ray: the statement is about the numbers the fine loop
+// would read, so the pixel's lateral deviation does not enter -- the window bounds account for it themselves.  Coarse samples
+// ProofMargins::cstep apart (8 voxels of the longest axis), each standing for the parameters within half a step of it, leave
+// 4.5 - 4 = 0.5 voxel for the rounding of t, of x = o + t d and of x * res (below 0.01 voxel, as for the fine stages) and for a sample
+// position that differs by an ulp between two builds.
+// Two walks, forward from t0 and backward from t1, each up to the first sample whose bound is at or below max(thr_hi, 0), give
+// [ta, tb]: at every fine position outside it the window minimum exceeds max(thr_hi, 0).  ta > tb: the whole ray is certified.
+struct ProofInterval { float ta, tb; };
+// What a replay counts per pixel (tools/sim_proof_interval.py through tests/harness); the device passes NoCount, which compiles to nothing.
+enum { DSDF_PC_ROUND, DSDF_PC_LIGHT, DSDF_PC_LEAP, DSDF_PC_BMIN, DSDF_PC_BMAX, DSDF_PC_VALUE, DSDF_PC_WALK, DSDF_PC_N };
+struct NoCount { DSDF_HD void add(int, int = 1) {} };
+template <class Count>
+DSDF_HD ProofInterval proof_interval(const GridView &G, const BoundGrid &Bc, const ProofRay &R, V3 o, V3 d, float cstep, Count &cnt) {
+    const float len = R.t1 - R.t0, thr = fmaxf(R.thr_hi, 0.f);
+    ProofInterval I = {INFINITY, -INFINITY};
+    // samples at distance s = 0, cstep, 2 cstep, .. from the walk's end of the ray, up to and including the first at or beyond the
+    // other end (clamped onto it): neighbours are at most cstep apart (four per round: the loads do not depend on each other)
+#pragma unroll
+    for (int back = 0; back < 2; ++back) {
+        bool found = false;
+        for (float sb = 0.f; sb < len + cstep && !found; sb += 4.f * cstep) {
+            float u[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float s = sb + (float)k * cstep;
+                const float t = back ? fmaxf(R.t1 - s, R.t0) : fminf(R.t0 + s, R.t1);
+                u[k] = s < len + cstep ? bound_at(Bc, G, fma3(t, d, o)) : INFINITY;
+                if (s < len + cstep) cnt.add(DSDF_PC_WALK);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (found || u[k] > thr) continue;          // (a NaN stops the walk)
+                found = true;
+                // the samples before this one cover what lies more than half a step before it
+                const float edge = sb + (float)k * cstep - 0.5f * cstep;
+                if (back) I.tb = fmaxf(fminf(R.t1 - edge, R.t1), R.t0);
+                else I.ta = fminf(fmaxf(R.t0 + edge, R.t0), R.t1);
+            }
+        }
+        if (!found) { I.ta = INFINITY; I.tb = -INFINITY; return I; }      // every sample of one walk clears: so does the whole ray
+    }
+    return I;
+}
+
 // Second and third stage of one listed pixel in ONE loop over the sample positions both proofs share (they start at the same t0 with
 // the same step): low byte = what `Bmin.b ? pixel_empty_proof(Bmin) : 0`, and where that is 0 and want_hit, pixel_hit_proof(Bmax)
 // return (tests/test_proof_value_host.py compares); bits 8.. = the same with the bounds tightened by the spline value (0 without
@@ -235,8 +286,18 @@ DSDF_HD ValueMargin value_margin(const ValueBound &vb) {
 // of the hit proof can only start earlier with a smaller landing bound -- so the loop ends when the third stage's minimum is at the
 // primal threshold and the second stage's hit proof is decided.  The value is evaluated only where the window straddles what it
 // has to clear (see the loop).
-DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, const BoundGrid &Bmax, const ValueBound &vb, const dsdf_params &P,
-                                   V3 o, V3 d, float step, bool want_hit) {
+// NEAR: only the rounds of that loop that hold a position inside [ta, tb] (proof_interval over the 8^3 minima Bc) run in full -- the
+// same flags (tests/test_proof_interval_host.py), from the same sample positions: tb advances by the same additions.  At a position
+// outside the interval lo > max(thr_hi, 0), so
+//   * m2 and m3 stay on the same side of both thresholds, and so do e_alive and the threshold need_e picks;
+//   * need_e is false (lo > thr_hi >= thr_p) and need_h is false (lo > 0 >= -mg.L): no value is evaluated, lo3 = lo, hi3 = hi;
+//   * hi3 = hi >= lo > 0: no run of the hit proof starts or goes on, and hit_run_step reduces to J = max(J, tc + half + hi).
+// Before ta the landing bound J of a LATER run still needs every hi, exactly: a light round loads the window maxima and folds them
+// into J (h3 == h2 there); a pixel without the hit proof only advances tb.  Beyond tb no run can start, J is never read again, and
+// the loop ends.  Every position before ta is < t1: live and not clamped.
+template <bool NEAR, class Count>
+DSDF_HD unsigned fine_proofs(const GridView &G, const BoundGrid &Bc, float cstep, const BoundGrid &Bmin, const BoundGrid &Bmax, const ValueBound &vb,
+                             const dsdf_params &P, V3 o, V3 d, float step, bool want_hit, Count &cnt) {
     const ProofRay R = proof_ray(P, o, d);
     if (!R.hit) return 0u;
     want_hit = want_hit && P.trace_eps > 0.f && R.in_hit;
@@ -247,10 +308,37 @@ DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, con
     float m2 = INFINITY, m3 = INFINITY;
     HitRun h2 = DSDF_HIT_RUN_INIT, h3 = h2;
     bool e_alive = want_empty;
-    for (float tb = t0; tb < t1 + step && (e_alive || (want_hit && !h2.done)); tb += 4.f * step) {
+    float tb = t0, tend = INFINITY;
+    if (NEAR) {
+        if (!want_empty && !want_hit) return 0u;
+        const ProofInterval I = proof_interval(G, Bc, R, o, d, cstep, cnt);
+        if (I.ta > I.tb) {        // nothing to find: both minima clear both thresholds, no run starts
+            const unsigned f = want_empty ? (DSDF_PX_EMPTY | DSDF_PX_EMPTY_G) : 0u;
+            return third ? (f | (f << 8)) : f;
+        }
+        if (want_hit) {
+            for (; tb + 3.f * step < I.ta; tb += 4.f * step) {
+                float tc[4], U[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    tc[k] = tb + (float)k * step;
+                    U[k] = bound_at(Bmax, G, fma3(tc[k], d, o));
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) h2.J = fmaxf(h2.J, tc[k] + half + U[k]);
+                cnt.add(DSDF_PC_LIGHT); cnt.add(DSDF_PC_BMAX, 4);
+            }
+            h3 = h2;
+        } else {
+            for (; tb + 3.f * step < I.ta; tb += 4.f * step) cnt.add(DSDF_PC_LEAP);
+        }
+        if (I.tb < t1) tend = I.tb;        // (tb == t1: the positions beyond t1 are clamped ONTO it, the loop runs to its own end)
+    }
+    for (; tb < t1 + step && (!NEAR || tb <= tend) && (e_alive || (want_hit && !h2.done)); tb += 4.f * step) {
         float tc[4], lo[4], hi[4], lo3[4], hi3[4];
         const bool v_alive = third && (e_alive || (want_hit && !h3.done));
         const bool fetch_lo = e_alive || v_alive;
+        cnt.add(DSDF_PC_ROUND);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const bool live = tb + (float)k * step < t1 + step;
@@ -258,6 +346,8 @@ DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, con
             const V3 x = fma3(tc[k], d, o);
             lo3[k] = lo[k] = fetch_lo && live ? bound_at(Bmin, G, x) : INFINITY;
             hi3[k] = hi[k] = want_hit ? bound_at(Bmax, G, x) : INFINITY;
+            if (fetch_lo && live) cnt.add(DSDF_PC_BMIN);
+            if (want_hit) cnt.add(DSDF_PC_BMAX);
             // (the value can only matter where the window minimum fails the threshold still in play -- the larger one until the
             // gradient flag is lost, then the primal's -- or, for the hit proof, where v + margin < 0 is possible: minimum < -margin
             // under a maximum >= 0)
@@ -267,6 +357,7 @@ DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, con
                 const float v = eval_value(G, x), m = mg.L + 4e-6f * (fabsf(v) + mg.tap);
                 lo3[k] = fmaxf(lo[k], v - m);
                 hi3[k] = fminf(hi[k], v + m);
+                cnt.add(DSDF_PC_VALUE);
             }
         }
         m2 = fminf(m2, fminf(fminf(lo[0], lo[1]), fminf(lo[2], lo[3])));
@@ -286,6 +377,18 @@ DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, con
     if (!f2 && want_hit && h2.done) f2 = DSDF_PX_HIT;
     if (!f3 && want_hit && h3.done) f3 = DSDF_PX_HIT;
     return third ? (f2 | (f3 << 8)) : f2;
+}
+// The reference form: every position from box entry to box exit ...
+DSDF_HD unsigned pixel_fine_proofs(const GridView &G, const BoundGrid &Bmin, const BoundGrid &Bmax, const ValueBound &vb, const dsdf_params &P,
+                                   V3 o, V3 d, float step, bool want_hit) {
+    NoCount none;
+    return fine_proofs<false>(G, Bmin, 0.f, Bmin, Bmax, vb, P, o, d, step, want_hit, none);
+}
+// ... and what the device runs: the stretch near the shape.  Bc: the dilated minima of the 8^3 level, cstep: ProofMargins::cstep.
+DSDF_HD unsigned pixel_fine_proofs_near(const GridView &G, const BoundGrid &Bc, float cstep, const BoundGrid &Bmin, const BoundGrid &Bmax,
+                                        const ValueBound &vb, const dsdf_params &P, V3 o, V3 d, float step, bool want_hit) {
+    NoCount none;
+    return fine_proofs<true>(G, Bc, cstep, Bmin, Bmax, vb, P, o, d, step, want_hit, none);
 }
 
 }  // namespace dsdf
@@ -361,9 +464,12 @@ static GridLayout grid_layout(int rx, int ry, int rz) {
 //   fstep  step of the fine stages on the window bounds, 0 when worst + half a step exceed their ONE voxel (0.01 voxel of slack on
 //          either side for the rounding of x * res), or the box argument fails
 //   reach  the r of the third stage's gradient bound (ValueBound, voxels) at fstep: worst + half a step + 0.01 -- at most 1
+//   cstep  step of the walks through the 8^3 minima that bracket the fine stages' loop (proof_interval): the dilated bound of a point's
+//          block reaches C = 8 voxels below and C - 1 above the point, a fine window 1.5 - DSDF_FINE_LO = 3.5 below and
+//          DSDF_FINE_HI - 0.5 = 2.5 above its position, both on the centre ray: half a step + 0.01 <= C - 3.5, capped at one block
 struct ProofMargins {
     int level;
-    float step0, step, hstep, fstep, reach;
+    float step0, step, hstep, fstep, reach, cstep;
 };
 static ProofMargins proof_margins(const dsdf_camera *cams, int nv, int W, int rx, int ry, int rz) {
     const int rmax = rx > ry ? (rx > rz ? rx : rz) : (ry > rz ? ry : rz);
@@ -383,7 +489,7 @@ static ProofMargins proof_margins(const dsdf_camera *cams, int nv, int W, int rx
         return step_vox / (float)rmax;
     };
     auto level_step = [&](int level) { const float C = (float)(1 << DSDF_COARSE_SHIFT(level)); return block_step(C, C); };
-    ProofMargins M = {-1, 0.f, 0.f, 0.f, 0.f, 0.f};
+    ProofMargins M = {-1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int level = DSDF_COARSE_LEVELS - 1; level >= 0 && M.level < 0; --level)
         if ((M.step = level_step(level)) > 0.f) M.level = level;
     if (M.level > 0) M.step0 = level_step(M.level - 1);
@@ -393,6 +499,12 @@ static ProofMargins proof_margins(const dsdf_camera *cams, int nv, int W, int rx
         if (!(step_vox < 0.25f)) M.fstep = (step_vox > 1.f ? 1.f : step_vox) / (float)rmax;
     }
     M.reach = worst + 0.5f * M.fstep * (float)rmax + 0.01f;
+    {
+        const float C = (float)(1 << DSDF_COARSE_SHIFT(0));
+        const float below = C - (1.5f - (float)DSDF_FINE_LO), above = (C - 1.f) - ((float)DSDF_FINE_HI - 0.5f);
+        const float step_vox = 2.f * ((below < above ? below : above) - 0.01f);
+        M.cstep = (step_vox > C ? C : step_vox) / (float)rmax;
+    }
     return M;
 }
 

@@ -105,7 +105,9 @@ __global__ void k_pixel_skip(GridView G, BoundGrid Bmin0, BoundGrid Bmin, BoundG
 // -+ a gradient bound (dsdf_proof.h: ValueBound).  What it proves beyond the second stage goes to `plane`, the library-private
 // effective plane, with the same bit meanings (7 / 1 / 4); `flags`, which a caller may read, is written byte for byte as without it.
 // (As a launch of its own over the pixels the second stage leaves it cost 1.0 + 1.6 ms per proof instead of 1.9: DESIGN 5.61.)
-__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bmin, BoundGrid B, ValueBound vb, dsdf_params P, ViewBatch VB,
+// The loop runs only over the stretch of the centre ray near the shape (dsdf_proof.h: proof_interval -- two short walks through the
+// dilated 8^3 minima Bc, cstep apart, in this kernel's preamble), with the flags of the whole ray.
+__global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bc, float cstep, BoundGrid Bmin, BoundGrid B, ValueBound vb, dsdf_params P, ViewBatch VB,
                                                         unsigned char *__restrict__ flags, unsigned char *__restrict__ plane,
                                                         const uint32_t *__restrict__ count, const uint32_t *__restrict__ list, float step,
                                                         int hit) {
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void k_pixel_hit_fine(GridView G, BoundGrid Bm
     const CamRay r = pixel_centre_ray(A.cam, P, px, py, A.W, A.H);
     const unsigned f = flags[e];
     // both stages, both proofs, one loop over the sample positions (dsdf_proof.h); the hit proof only for the pixels without bit 0
-    const unsigned m = pixel_fine_proofs(G, Bmin, B, vb, P, r.o, r.d, step, hit && !(f & DSDF_PX_EMPTY));
+    const unsigned m = pixel_fine_proofs_near(G, Bc, cstep, Bmin, B, vb, P, r.o, r.d, step, hit && !(f & DSDF_PX_EMPTY));
     const unsigned add = px_fine_bits(m & 0xffu), add3 = px_fine_bits(m >> 8);
     if (add) flags[e] = (unsigned char)(f | add);
     // the third stage's results never reach the caller-visible byte: the render stages read them from the effective plane
