@@ -192,9 +192,10 @@ struct Queue {
     uint32_t rows;
     uint32_t cap;     // slots per view (= nunits * 64)
     uint32_t nunits;  // units per view
-    uint32_t coef_rows;   // 8 (silhouette) or DSDF_COEF_WORDS
+    uint32_t coef_rows;   // coef_block_rows(integrator): 8 (silhouette) or DSDF_COEF_WORDS coefficient rows, then its_t and warp_t
     float *coef;      // coef_rows rows (SoA, stride = cap), indexed by QUEUE SLOT: the image-independent half of the adjoint
-                      // (k_backward_coef -> k_backward_apply); nullptr for sdf_direct_reparam
+                      // and the two distances that locate the scatter points (k_backward_coef -> k_backward_apply); nullptr for
+                      // sdf_direct_reparam
 };
 
 // Views of one launch (grid.y = view): all sensors of a batch are traced by ONE kernel so
@@ -688,19 +689,24 @@ __global__ void k_develop_aov(const float *__restrict__ blocks, int W, int H, fl
 #ifndef DSDF_BWD_UNITS
 #define DSDF_BWD_UNITS 16
 #endif
+static_assert(DSDF_BWD_UNITS <= 64, "one count per lane");
 struct UnitGather {
     uint32_t c[DSDF_BWD_UNITS], lo[DSDF_BWD_UNITS], total, unit0;
     // the queued samples [from[u], count[u]) of the group's units (from == nullptr: all of them)
     // (`upto`: the counts to use instead of q.count -- a snapshot of them, while another kernel is still appending)
+    // Lane k loads the numbers of unit k, readlane hands them to the wave: one round trip (16 scalarised loads, each with its own
+    // wait, before).
     __device__ __forceinline__ void init(const Queue &q, uint32_t group, const uint32_t *from = nullptr, const uint32_t *upto = nullptr) {
         unit0 = group * (uint32_t)DSDF_BWD_UNITS;
         total = 0;
         const uint32_t *cnt = upto ? upto : q.count;
+        const uint32_t k0 = threadIdx.x & 63u;
+        const bool in = k0 < (uint32_t)DSDF_BWD_UNITS && unit0 + k0 < q.nunits;
+        const uint32_t vn = in ? cnt[unit0 + k0] : 0u, vf = (in && from) ? from[unit0 + k0] : 0u;
 #pragma unroll
         for (int k = 0; k < DSDF_BWD_UNITS; ++k) {
-            const bool in = unit0 + k < q.nunits;
-            const uint32_t n = in ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt[unit0 + k]) : 0u;
-            lo[k] = (in && from) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)from[unit0 + k]) : 0u;
+            const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)vn, k);
+            lo[k] = (uint32_t)__builtin_amdgcn_readlane((int)vf, k);
             c[k] = n - (lo[k] < n ? lo[k] : n);
             total += c[k];
         }
@@ -837,6 +843,9 @@ __global__ __launch_bounds__(64, DSDF_COEF_MINWAVES) void k_backward_coef(GridVi
             o[8 * cs] = c.U.x; o[9 * cs] = c.U.y; o[10 * cs] = c.U.z; o[11 * cs] = c.k0;
             o[12 * cs] = c.W.x; o[13 * cs] = c.W.y; o[14 * cs] = c.W.z; o[15 * cs] = c.val;
         }
+        // ... and where the sample's scatter points lie, by slot (dsdf_lane.h: DSDF_COEF_POS_ROWS)
+        const size_t pos = (size_t)(q.coef_rows - DSDF_COEF_POS_ROWS) * cs;
+        o[pos] = tr.its_t; o[pos + cs] = tr.warp_t;
     }
 }
 
@@ -858,13 +867,13 @@ __global__ __launch_bounds__(64) void k_backward_apply(GridView G, dsdf_params P
         if (si < count) {
             const uint32_t slot = ug.slot(si), lane = q.lane[slot];
             const float *o = q.coef + slot;
-            const size_t cs = q.cap;
+            const size_t cs = q.cap, pos = (size_t)(q.coef_rows - DSDF_COEF_POS_ROWS) * cs;
             BackCoef c;
             c.flags = __float_as_uint(o[0]);
             c.cdir = mk(o[cs], o[2 * cs], o[3 * cs]); c.a = o[4 * cs]; c.b = mk(o[5 * cs], o[6 * cs], o[7 * cs]);
             TraceOut tr;
-            clear_trace_out(tr, q.rec[lane]);                    // its_t ...
-            tr.warp_t = q.rec[lane + q.cap];                     // ... and warp_t locate the two scatter points
+            clear_trace_out(tr, o[pos]);                         // its_t ...
+            tr.warp_t = o[pos + cs];                             // ... and warp_t locate the two scatter points
             if (A.integrator == DSDF_SIMPLE_SHADING) {
                 c.U = mk(o[8 * cs], o[9 * cs], o[10 * cs]); c.k0 = o[11 * cs];
                 c.W = mk(o[12 * cs], o[13 * cs], o[14 * cs]); c.val = o[15 * cs];
@@ -996,7 +1005,7 @@ static Workspace carve(void *base, int W, int H, int spp, int nv, int integrator
         ws.qlane = (uint32_t *)(p + off); off += align_up(nv * cap * sizeof(uint32_t), 256);
         ws.qrec = (float *)(p + off); off += align_up(nv * cap * rows * sizeof(float), 256);
         if (integrator != DSDF_DIRECT) {
-            ws.coef_rows = integrator == DSDF_SILHOUETTE ? 8 : DSDF_COEF_WORDS;         // (the silhouette integrator uses the first 8 rows)
+            ws.coef_rows = coef_block_rows(integrator);      // (8 or DSDF_COEF_WORDS coefficient rows + its_t, warp_t: dsdf_lane.h)
             ws.qcoef = (float *)(p + off); off += align_up(nv * cap * ws.coef_rows * sizeof(float), 256);
             ws.count0 = (uint32_t *)(p + off); off += align_up(nv * nunits * sizeof(uint32_t), 256);
         }

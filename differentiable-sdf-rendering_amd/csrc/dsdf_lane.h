@@ -162,6 +162,57 @@ DSDF_HD FilmAdjoint<NV> film_gather(const float *block_adj, int Wb, int Hb, floa
     return a;
 }
 
+// The same gather with the loads of ROWS rows of the footprint in ONE round.  Behind film_taps_each's bounds tests the compiler
+// waits for the load of each tap before it issues the next: 16 dependent round trips per sample in the latency-bound
+// k_backward_apply.  Here every tap of the rows is read first -- a tap outside the block from the nearest pixel
+// inside it, its value unused -- and the sums then run over the taps inside the block in film_gather's order and with
+// film_gather's statements: the same result to the bit.  4 ROWS (NV + 1) registers hold the taps of a round.
+#ifndef DSDF_APPLY_GATHER_ROWS
+#define DSDF_APPLY_GATHER_ROWS 4   /* lane_backward_apply: the whole footprint in one round, 32 registers */
+#endif
+template <int NV, int ROWS>
+DSDF_HD FilmAdjoint<NV> film_gather_rounds(const float *block_adj, int Wb, int Hb, float u, float v, const float *vals) {
+    static_assert(4 % ROWS == 0, "whole rounds");
+    FilmAdjoint<NV> a;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) a.a_c[c] = 0.f;
+    a.a_w = 0.f; a.u_bar = 0.f; a.v_bar = 0.f;
+    const FilmTaps<true> T = film_taps<true>(u, v);
+#pragma unroll
+    for (int j0 = 0; j0 < 4; j0 += ROWS) {
+        float ba[ROWS][4][NV + 1];
+#pragma unroll
+        for (int jj = 0; jj < ROWS; ++jj) {
+            const size_t row = (size_t)iclamp(T.y0 + j0 + jj, 0, Hb - 1) * Wb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float *p = block_adj + (NV + 1) * (row + iclamp(T.x0 + i, 0, Wb - 1));
+#pragma unroll
+                for (int c = 0; c <= NV; ++c) ba[jj][i][c] = p[c];
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < ROWS; ++jj) {
+            const int j = j0 + jj, qy = T.y0 + j;
+            if (qy < 0 || qy >= Hb) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int qx = T.x0 + i;
+                if (qx < 0 || qx >= Wb) continue;
+                const float *t = ba[jj][i];
+                float f = T.wx[i] * T.wy[j];
+                float s = t[NV];
+#pragma unroll
+                for (int c = 0; c < NV; ++c) { a.a_c[c] = fmaf(f, t[c], a.a_c[c]); s = fmaf(t[c], vals[c], s); }
+                a.a_w = fmaf(f, t[NV], a.a_w);
+                a.u_bar = fmaf(s, -T.dwx[i] * T.wy[j], a.u_bar);   // d f / d u = -F'(rel_x) F(rel_y)
+                a.v_bar = fmaf(s, -T.wx[i] * T.dwy[j], a.v_bar);
+            }
+        }
+    }
+    return a;
+}
+
 // ---------------------------------------------------------------------------
 // Forward mode (`ReparamIntegrator.render_forward`, integrators/reparam.py:192-196; used by the reference's
 // gradient-image validation, figures/result_utils.py:126-161, with the tangent on `sdf.p`): the tangent of one
@@ -751,6 +802,13 @@ DSDF_HD bool lane_backward_direct(const GridView &G, const dsdf_params &P, const
 //   shading channel: G-bar = a_val U,  v_0-bar = a_val k0,  d'-bar += a_val W      (U, k0, W carry the [n.l > 0] indicator)
 // ---------------------------------------------------------------------------
 #define DSDF_COEF_WORDS 16
+// Rows of the coefficient block of a queue slot: the words of BackCoef the integrator uses (silhouette: the first 8), then
+// DSDF_COEF_POS_ROWS rows with the sample's its_t and warp_t, which locate its two scatter points.  They are copies of the first
+// two words of the sample's record: the record is indexed by LANE, one load behind q.lane[slot], the block by SLOT -- with them
+// the apply half loads everything of a sample in one round.
+#define DSDF_COEF_POS_ROWS 2
+DSDF_HD constexpr uint32_t coef_value_rows(int integrator) { return integrator == DSDF_SILHOUETTE ? 8u : (uint32_t)DSDF_COEF_WORDS; }
+DSDF_HD constexpr uint32_t coef_block_rows(int integrator) { return coef_value_rows(integrator) + (uint32_t)DSDF_COEF_POS_ROWS; }
 struct BackCoef { uint32_t flags; V3 cdir; float a; V3 b; V3 U; float k0; V3 W; float val; };   // flags: 1 warp, 2 shading
 
 DSDF_HD bool lane_backward_coef(const GridView &G, const dsdf_params &P, const ViewArgs &A, const Lane &L, const TraceOut &tr,
@@ -790,7 +848,7 @@ DSDF_HD bool lane_backward_apply(const dsdf_params &P, const ViewArgs &A, const 
     const V3 o = L.ray.o, d = L.ray.d;
     Reproj rp = reproject(A.cam, P, o + d, A.W, A.H);
     const float val = c.val;
-    const FilmAdjoint<1> fa = film_gather<1>(block_adj, A.Wb, A.Hb, rp.u, rp.v, &val);
+    const FilmAdjoint<1> fa = film_gather_rounds<1, DSDF_APPLY_GATHER_ROWS>(block_adj, A.Wb, A.Hb, rp.u, rp.v, &val);
     const float a_val = fa.a_c[0];
     const float div_bar = val * a_val + fa.a_w;
     V3 dir_bar = reproject_adjoint(A.cam, A.W, rp, fa.u_bar, fa.v_bar, div_bar);

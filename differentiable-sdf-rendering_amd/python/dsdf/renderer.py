@@ -1138,7 +1138,7 @@ def eager_sweep_enabled():
     sequential gradient pass.  Default 1 (the optimiser loop's fast path).  What the eager schedule costs, so that a caller can
     decide: a grad-enabled render that is never back-propagated (a validation image rendered without torch.no_grad()) pays a
     gradient sweep it does not need, and every render whose backward is still outstanding keeps its backward queue (40 B per
-    gradient-pass sample and view: 8.2 GB + 6.5 GB of coefficients for 12 views x 512^2 x 64 spp) until its backward ran or
+    gradient-pass sample and view: 8.2 GB + 8.2 GB of coefficients for 12 views x 512^2 x 64 spp) until its backward ran or
     its graph is freed; several such renders hold a queue each (the first leases the cached buffer, the others allocate)."""
     return os.environ.get('DSDF_EAGER_SWEEP', '1') != '0'
 
