@@ -865,6 +865,7 @@ class MeshBvh:
                 raise _lib.DsdfError("colors must live on the device of the triangles")
         self.device, self.n_triangles, self.has_normals = tri.device, T, nrm is not None
         self.triangles = tri.reshape(T, 3, 3)        # (the caller's order: what mesh_distance samples)
+        self.moments = None                          # (the per-node moments of `winding`, built on first use)
         self.buffer = torch.empty(int(lib.dsdf_mesh_bvh_size(T, int(nrm is not None))), dtype=torch.float32, device=tri.device)
         codes = torch.empty(T, dtype=torch.int32, device=tri.device)
         with torch.cuda.device(tri.device):
@@ -891,14 +892,43 @@ class MeshBvh:
         return _closest(lambda lib, *a: lib.dsdf_mesh_bvh_closest(_ptr(self.buffer), *a), self.device, points, max_dist, return_prim,
                         return_point, return_bary)
 
+    def winding(self, points, beta=2.0):
+        """The generalized winding number of the mesh at `points` (N,3) -> (N,) float32, through the hierarchy (dsdf_mesh_bvh_winding): a
+        subtree farther than beta x its radius counts as one dipole.  beta >= 1; float('inf') is the exact sum (mesh_winding up to the order
+        of the terms); the default 2 stays within 0.1 of it.  The moments buffer is built on first use and kept on the object."""
+        lib = _lib.load()
+        pts = _points(points, self.device)
+        if not float(beta) >= 1.0:
+            raise _lib.DsdfError(f"dsdf_mesh_bvh_winding: beta must be >= 1, got {beta}")
+        with torch.cuda.device(self.device):
+            if self.moments is None:
+                mom = torch.empty(int(lib.dsdf_mesh_bvh_moments_size(self.n_triangles)), dtype=torch.float32, device=self.device)
+                _lib.check(lib.dsdf_mesh_bvh_moments(_ptr(self.buffer), self.n_triangles, _ptr(mom), _stream()))
+                self.moments = mom
+            w = torch.empty(int(pts.shape[0]), dtype=torch.float32, device=self.device)
+            _lib.check(lib.dsdf_mesh_bvh_winding(_ptr(self.buffer), _ptr(self.moments), _ptr(pts), int(pts.shape[0]), C.c_float(beta), _ptr(w),
+                                                 _stream()))
+        return w
 
-def _closest(entry, device, points, max_dist, return_prim, return_point, return_bary):
-    lib = _lib.load()
+    def signed_distance(self, points, beta=2.0):
+        """The signed distance of `points` (N,3) to the mesh from two queries: `closest`, negated where `winding(points, beta)` > 0.5 (the
+        renderer's convention: negative inside)."""
+        d = self.closest(points)
+        return torch.where(self.winding(points, beta) > 0.5, -d, d)
+
+
+def _points(points, device):
     if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
         raise _lib.DsdfError(f"points must be (N,3), got {tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
     pts = _require_dev(points, 'points')
     if pts.device != device:
         raise _lib.DsdfError("points must live on the device of the mesh")
+    return pts
+
+
+def _closest(entry, device, points, max_dist, return_prim, return_point, return_bary):
+    lib = _lib.load()
+    pts = _points(points, device)
     n = int(pts.shape[0])
     dist = torch.empty(n, dtype=torch.float32, device=device)
     prim = torch.empty(n, dtype=torch.int32, device=device) if return_prim else None
@@ -920,6 +950,39 @@ def mesh_closest(triangles, points, max_dist=float('inf'), return_prim=False, re
         raise _lib.DsdfError("mesh_closest needs at least one triangle")
     return _closest(lambda lib, *a: lib.dsdf_mesh_closest(_ptr(tri), int(tri.shape[0]), *a), tri.device, points, max_dist, return_prim,
                     return_point, return_bary)
+
+
+def mesh_winding(triangles, points):
+    """The generalized winding number of a triangle soup (T,3,3) at `points` (N,3) -> (N,) float32: the exact sum of the signed solid angles
+    over 4 pi, every point against every triangle (dsdf_mesh_winding; MeshBvh.winding serves large meshes).  1 inside an outward-oriented
+    closed mesh, 0 outside; w > 0.5 is the inside test for an open or self-intersecting one."""
+    lib = _lib.load()
+    tri = _require_dev(triangles.reshape(-1, 9), 'triangles')
+    if tri.shape[0] < 1:
+        raise _lib.DsdfError("mesh_winding needs at least one triangle")
+    pts = _points(points, tri.device)
+    w = torch.empty(int(pts.shape[0]), dtype=torch.float32, device=tri.device)
+    with torch.cuda.device(tri.device):
+        _lib.check(lib.dsdf_mesh_winding(_ptr(tri), int(tri.shape[0]), _ptr(pts), int(pts.shape[0]), _ptr(w), _stream()))
+    return w
+
+
+BVH_MIN_TRIANGLES = 4096    # a mesh given as a tensor goes through a MeshBvh above this, through the brute-force kernels below (mesh_to_sdf shares it)
+
+
+def mesh_signed_distance(mesh, points, beta=2.0):
+    """The signed distance of `points` (N,3) to a mesh, negative inside: the `closest` distance, negated where the winding number exceeds
+    0.5.  `mesh`: a MeshBvh, or (T,3,3) triangles -- above BVH_MIN_TRIANGLES (4096, the threshold of mesh_to_sdf) they go through a MeshBvh built
+    for the call (`beta` as in MeshBvh.winding), below it through the two brute-force kernels (exact sum)."""
+    if isinstance(mesh, MeshBvh):
+        return mesh.signed_distance(points, beta)
+    tri = _require_dev(mesh.reshape(-1, 9), 'mesh')
+    if not float(beta) >= 1.0:
+        raise _lib.DsdfError(f"mesh_signed_distance: beta must be >= 1, got {beta}")
+    if tri.shape[0] > BVH_MIN_TRIANGLES:
+        return MeshBvh(tri).signed_distance(points, beta)
+    d = mesh_closest(tri, points)
+    return torch.where(mesh_winding(tri, points) > 0.5, -d, d)
 
 
 def sample_surface(triangles, n, seed=0):

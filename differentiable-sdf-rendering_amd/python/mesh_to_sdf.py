@@ -14,7 +14,7 @@ import dsdf
 import redistancing
 
 ANGULAR_RES = 16            # mesh_to_sdf.py:40: 16 x 16 stratified directions per near-surface voxel
-BVH_MIN_TRIANGLES = 4096    # accel=None: meshes above this go through dsdf.MeshBvh, smaller ones through the brute-force kernel
+BVH_MIN_TRIANGLES = dsdf.renderer.BVH_MIN_TRIANGLES    # (4096) accel=None: meshes above this go through dsdf.MeshBvh, smaller ones through the brute-force kernel
 
 
 def load_obj(fn, colors=False):
@@ -273,14 +273,36 @@ def _caster(triangles, accel=None):
     return lambda o, d: dsdf.mesh_raycast(triangles, o, d)
 
 
-def occupancy(triangles, res, cast=None):
+def _winder(triangles, accel=None):
+    """points -> winding number of this mesh.  accel as in _caster: 'brute' = dsdf.mesh_winding (the exact sum), 'bvh' =
+    dsdf.MeshBvh.winding (beta = 2: within 0.1 of it), None = the BVH above BVH_MIN_TRIANGLES triangles."""
+    if accel not in (None, 'bvh', 'brute'):
+        raise ValueError(f"accel must be None, 'bvh' or 'brute', got {accel!r}")
+    if accel == 'bvh' or (accel is None and triangles.shape[0] > BVH_MIN_TRIANGLES):
+        return dsdf.MeshBvh(triangles).winding
+    return lambda x: dsdf.mesh_winding(triangles, x)
+
+
+def _check_sign(sign):
+    if sign not in ('rays', 'winding'):
+        raise ValueError(f"sign must be 'rays' or 'winding', got {sign!r}")
+
+
+def occupancy(triangles, res, cast=None, sign='rays', accel=None):
     """0.5 - inside, inside = the +y ray from the voxel centre leaves the solid through its first hit (mesh_to_sdf.py:23-27).
     The reference casts that one ray with Embree / OptiX, whose intersectors are edge-consistent; dsdf_mesh_raycast tests every
     triangle on its own (Moeller-Trumbore), so a ray through a shared edge or vertex -- voxel centres sit on the symmetry planes
     of many meshes -- can slip between two triangles.  The -y ray answers the same question (a watertight mesh is left
-    through a back face in every direction); where the two disagree a third, generic direction decides."""
+    through a back face in every direction); where the two disagree a third, generic direction decides.
+    sign='winding' (opt-in; 'rays' is the reference's method and needs a watertight, consistently oriented mesh without
+    self-intersections): inside = the generalized winding number of the voxel centre exceeds 0.5 (_winder(triangles, accel); `cast` is
+    not used) -- a mesh with holes or overlapping parts gets the sign a ray would leak along its direction."""
+    _check_sign(sign)
     dev = triangles.device
     o = voxel_centres(res, dev)
+    if sign == 'winding':
+        inside = _winder(triangles, accel)(o) > 0.5
+        return (0.5 - inside.float()).reshape(res, res, res), o
     cast = cast or _caster(triangles, 'brute')
 
     def inside_along(direction):
@@ -340,18 +362,48 @@ def refine(triangles, grid, origins, res, chunk=1 << 16, cast=None, distance='ra
     return flat.reshape(res, res, res)
 
 
-def create_sdf(mesh_fn, resolution, refine_surface=True, device='cuda', accel=None, distance='rays'):
+def create_sdf(mesh_fn, resolution, refine_surface=True, device='cuda', accel=None, distance='rays', sign='rays'):
     """Convert a watertight mesh to an SDF using ray casting and redistancing.  `mesh_fn`: path of an obj / ply file, or a
     (T, 3, 3) tensor / array of triangle corners.  accel: how the rays are cast (_caster); the result does not depend on it.
     distance: how `refine` measures the near-surface voxels -- 'rays' (the reference's 256 directions, the default) or 'closest' (the
-    exact distance from one closest-point query)."""
+    exact distance from one closest-point query).  sign: how `occupancy` tells inside from outside -- 'rays' (the reference's first-hit
+    test, the default) or 'winding' (the generalized winding number: any triangle soup); everything after the occupancy is the same."""
     _check_distance(distance)
+    _check_sign(sign)
     tri = load_mesh(mesh_fn) if isinstance(mesh_fn, str) else mesh_fn
     tri = torch.as_tensor(np.asarray(tri) if not torch.is_tensor(tri) else tri, dtype=torch.float32).to(device).reshape(-1, 3, 3).contiguous()
     res = int(resolution)
     cast = _caster(tri, accel)
-    values, origins = occupancy(tri, res, cast)
+    values, origins = occupancy(tri, res, cast, sign=sign, accel=accel)
     grid = redistancing.redistance(values)
     if refine_surface:
         grid = redistancing.redistance(refine(tri, grid, origins, res, cast=cast, distance=distance, accel=accel))
     return grid
+
+
+def parse_args(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description='Triangle mesh (obj / ply, inside [-0.5, 0.5]^3) -> SDF grid, written as a .vol.')
+    ap.add_argument('mesh')
+    ap.add_argument('-o', '--out', required=True, help='the .vol file to write')
+    ap.add_argument('--res', type=int, default=128)
+    ap.add_argument('--sign', choices=('rays', 'winding'), default='rays',
+                    help="rays: first-hit test (watertight meshes); winding: generalized winding number (any triangle soup)")
+    ap.add_argument('--distance', choices=('rays', 'closest'), default='rays')
+    a = ap.parse_args(argv)
+    if a.res < 2:
+        ap.error('--res must be at least 2')
+    return a
+
+
+def main(argv=None):
+    import util
+    a = parse_args(argv)
+    grid = create_sdf(a.mesh, a.res, distance=a.distance, sign=a.sign)
+    util.write_vol(a.out, grid.cpu())
+    print(f'{a.out}: {a.res}^3, sign={a.sign}, distance={a.distance}')
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

@@ -463,6 +463,24 @@ int dsdf_mesh_closest(const float *triangles, int n_triangles, const float *poin
 int dsdf_mesh_bvh_closest(const float *bvh, const float *points, int64_t n, float max_dist,
                           float *dist_out, int32_t *prim_out, float *point_out, float *bary_out, void *stream);
 
+/* ---- generalized winding number (csrc/dsdf_winding.h): on which side of a mesh a point lies, for ANY triangle soup ----
+ * w(x) = (1 / 4 pi) x the sum of the signed solid angles of the triangles seen from x: the integer number of times a closed mesh wraps
+ * x (1 inside an outward-oriented one -- normals (p1 - p0) x (p2 - p0) pointing out --, 0 outside), a smooth function for an open or
+ * self-intersecting one; w > 0.5 is the inside test.  points n x 3, w_out n.  A point ON a triangle gets a finite value of no accuracy.
+ * dsdf_mesh_winding: the exact sum, every point against every triangle (small meshes; the yardstick of the tree).
+ * dsdf_mesh_bvh_winding: the same sum over the tree of a BVH buffer, with a subtree whose centre c lies farther than beta x its radius
+ * from x replaced by its dipole N . (c - x) / (4 pi |c - x|^3).  beta >= 1; +INFINITY: the exact sum; 2 keeps the error below 0.1 on
+ * every mesh of the tests (profiles/mesh_winding.md).  It reads the per-node moments from a SECOND caller-owned buffer of
+ * dsdf_mesh_bvh_moments_size() floats (64-byte aligned; the BVH buffer itself is unchanged), filled once per BVH by
+ * dsdf_mesh_bvh_moments (n_triangles as given to dsdf_mesh_bvh_build): 8 floats per heap node, leaves included -- the record of heap
+ * node i at 8 (i + 1): N.xyz = sum 1/2 e1 x e2, c.xyz = the area-weighted centroid, r = a radius around c that holds the subtree's
+ * triangles (-1: empty subtree), A = the total area (0: triangles without area, always descended into); floats [0, 8): int L, 7 x 0.
+ * n = 0 returns DSDF_OK without a launch.  Nothing here allocates or synchronises. */
+int dsdf_mesh_winding(const float *triangles, int n_triangles, const float *points, int64_t n, float *w_out, void *stream);
+size_t dsdf_mesh_bvh_moments_size(int n_triangles);
+int dsdf_mesh_bvh_moments(const float *bvh, int n_triangles, float *moments_out, void *stream);
+int dsdf_mesh_bvh_winding(const float *bvh, const float *moments, const float *points, int64_t n, float beta, float *w_out, void *stream);
+
 /* Primal render of the mesh: dsdf_render_forward with the intersection routine swapped -- same lane order, sampler rules (offsets /
  * seeds), camera ray, film block, re-projection and develop; no reparameterisation (det = 1).  Per sample: DSDF_SILHOUETTE [hit];
  * DSDF_SIMPLE_SHADING max(n . prm->light_dir, 0); DSDF_DIRECT the emitter-sampling statement of sdf_direct_reparam.py:29-75 with the
