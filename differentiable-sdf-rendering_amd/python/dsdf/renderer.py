@@ -9,7 +9,7 @@ from an independent (seed_grad, spp_grad) re-render
 """
 import contextlib
 import ctypes as C
-
+import math
 import os
 
 import torch
@@ -1141,6 +1141,114 @@ def extract_mesh(grid, resolution=None, iso=0.0, steps=24, normals=True, colors=
             raise _lib.DsdfError(f"colors must be a reflectance volume (Z,Y,X,3), got {tuple(colors.shape)}")
         out += (sample_volume(colors, pos),)
     return out
+
+
+SIMPLIFY_REG = 1e-3         # DSDF_SIMPLIFY_REG of csrc/dsdf_simplify.h
+SIMPLIFY_GROW = 2.0 ** -13  # the default box of simplify_mesh: the mesh AABB grown by this share of its largest extent on every side
+
+
+def resolve_cells(cells, lo, hi):
+    """(cx, cy, cz) of simplify_mesh's `cells`: a triple as it is; an int = that many cells along the longest extent of the box lo / hi and
+    cubic cells of that size on the other axes, ceil(extent / size), at least 1."""
+    if isinstance(cells, (tuple, list)):
+        c = tuple(int(v) for v in cells)
+        if len(c) != 3 or min(c) < 1:
+            raise _lib.DsdfError(f"cells must be an int >= 1 or three of them, got {cells!r}")
+        return c
+    n = int(cells)
+    if n < 1:
+        raise _lib.DsdfError(f"cells must be an int >= 1 or three of them, got {cells!r}")
+    ext = [float(h) - float(l) for l, h in zip(lo, hi)]
+    size = max(ext) / n
+    return tuple(n if e == max(ext) else min(n, max(1, math.ceil(e / size))) for e in ext)
+
+
+def simplify_mesh(vertices, faces, cells, bounds=None, normals=False, colors=None, reg=SIMPLIFY_REG):
+    """Simplifies an indexed triangle mesh by vertex clustering with quadric error metrics (Lindstrom 2000; include/dsdf.h: dsdf_simplify_*,
+    csrc/dsdf_simplify.h) -> (vertices' (V', 3) float32, faces' (F', 3) int32[, normals' (V', 3)][, colors' (V', 3)]) on the input's device.
+    All vertices in one cell of a regular grid become one vertex, placed where the summed squared distance to the planes of the cell's
+    triangles is smallest (regularised towards the mean of the cell's corners by `reg`) and clamped into the cell; a face whose corners do
+    not end up in three different cells disappears.  vertices (V, 3) float32, faces (F, 3) int32 (int64 is converted).
+    `cells`: (cx, cy, cz), or an int: that many along the longest extent of the box, cubic cells on the other axes.  `bounds` = (lo, hi): the
+    box of the grid -- pass the same one for two meshes to put them on one grid; default: the AABB of `vertices` grown by 2^-13 of its
+    largest extent (an axis without extent still has a box).  A vertex outside the box counts to the border cell.
+    `normals=True`: the normalised area-weighted normal sum of each cell's triangles (zero where it vanishes); `colors` (V, 3): their mean
+    over the cell's face corners.  Output vertices come in ascending cell order, output faces are the survivors in input order with their
+    winding kept.  Every output face is an input face with its corners moved inside their cells, so the result lies within one cell
+    diagonal of the input, and a closed input keeps its winding number at every point farther away than that.  Duplicate faces, and the
+    opposite pairs a collapsing thin sheet leaves, are KEPT as they are, and non-manifold edges can appear.  No faces, or all of them
+    collapsed: empty tensors of the right shapes.  The sort of the corner keys and the scans between the launches are torch (plumbing); the
+    counts are read back to size the outputs -- the call synchronises there."""
+    lib = _lib.load()
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise _lib.DsdfError(f"vertices must be (V,3), got {tuple(vertices.shape) if isinstance(vertices, torch.Tensor) else type(vertices).__name__}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.DsdfError(f"faces must be (F,3), got {tuple(faces.shape) if isinstance(faces, torch.Tensor) else type(faces).__name__}")
+    vert = _require_dev(vertices, 'vertices')
+    dev = vert.device
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise _lib.DsdfError(f"faces must be int32 (or int64), got {faces.dtype}")
+    fac = _require_dev(faces.to(torch.int32), 'faces', torch.int32)
+    if fac.device != dev:
+        raise _lib.DsdfError("faces must live on the device of the vertices")
+    col = None
+    if colors is not None:
+        if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != tuple(vert.shape):
+            raise _lib.DsdfError(f"colors must be (V,3) like vertices, got {tuple(colors.shape) if isinstance(colors, torch.Tensor) else type(colors).__name__}")
+        col = _require_dev(colors, 'colors')
+        if col.device != dev:
+            raise _lib.DsdfError("colors must live on the device of the vertices")
+    if not (float(reg) > 0.0 and float(reg) < float('inf')):
+        raise _lib.DsdfError(f"simplify_mesh: reg must be > 0, got {reg}")
+    V, F = int(vert.shape[0]), int(fac.shape[0])
+    if 3 * F >= 2 ** 31:
+        raise _lib.DsdfError(f"simplify_mesh: {F} faces: 3 F must stay below 2^31")
+    if F > 0 and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise _lib.DsdfError("simplify_mesh: face index out of range")
+    if bounds is not None:
+        lo, hi = ([float(v) for v in b] for b in bounds)
+    elif V > 0:
+        lo_t, hi_t = vert.amin(0).double(), vert.amax(0).double()
+        grow = SIMPLIFY_GROW * float((hi_t - lo_t).max())
+        lo, hi = (lo_t - grow).float().tolist(), (hi_t + grow).float().tolist()
+        if not all(h > l for l, h in zip(lo, hi)):                 # a single point (or non-finite vertices): any box around it
+            lo, hi = [l - 1.0 for l in lo], [h + 1.0 for h in hi]
+    else:
+        lo, hi = [0.0] * 3, [1.0] * 3
+    if len(lo) != 3 or len(hi) != 3:
+        raise _lib.DsdfError("bounds must be (lo, hi) with three numbers each")
+    cx, cy, cz = resolve_cells(cells, lo, hi)
+    lo_c, hi_c = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+    empty = lambda dt=torch.float32: torch.empty(0, 3, dtype=dt, device=dev)
+    result = lambda v, f, n, c: (v, f) + ((n,) if normals else ()) + ((c,) if colors is not None else ())
+    with torch.cuda.device(dev):
+        st = _stream()
+        keys = torch.empty(3 * F, dtype=torch.int32, device=dev)
+        _lib.check(lib.dsdf_simplify_keys(_ptr(vert), _ptr(fac), F, lo_c, hi_c, cx, cy, cz, _ptr(keys), st))       # (refuses a bad grid for F = 0 too)
+        if F == 0:
+            return result(empty(), empty(torch.int32), empty(), empty())
+        sorted_keys, order = torch.sort(keys, stable=True)
+        corner = order.to(torch.int32)
+        cell_keys, counts = torch.unique_consecutive(sorted_keys, return_counts=True)
+        U = int(cell_keys.shape[0])
+        cell_start = torch.zeros(U + 1, dtype=torch.int32, device=dev)
+        cell_start[1:] = torch.cumsum(counts, 0)
+        rank = torch.empty(3 * F, dtype=torch.int32, device=dev)
+        keep = torch.empty(F, dtype=torch.int32, device=dev)
+        used = torch.zeros(U, dtype=torch.int32, device=dev)
+        _lib.check(lib.dsdf_simplify_mark(_ptr(keys), F, _ptr(cell_keys), U, _ptr(rank), _ptr(keep), _ptr(used), st))
+        v_end, f_end = torch.cumsum(used, 0, dtype=torch.int32), torch.cumsum(keep, 0, dtype=torch.int32)
+        Vn, Fn = (int(v) for v in torch.stack([v_end[-1], f_end[-1]]).tolist())
+        faces_out = torch.empty(Fn, 3, dtype=torch.int32, device=dev)
+        pos = torch.empty(Vn, 3, dtype=torch.float32, device=dev)
+        nrm = torch.empty(Vn, 3, dtype=torch.float32, device=dev) if normals else None
+        col_out = torch.empty(Vn, 3, dtype=torch.float32, device=dev) if col is not None else None
+        if Fn > 0:
+            vertex_id, face_offset = v_end - used, f_end - keep
+            _lib.check(lib.dsdf_simplify_emit(_ptr(vert), _ptr(fac), F, _ptr(col), lo_c, hi_c, cx, cy, cz, C.c_float(float(reg)), _ptr(corner),
+                                              _ptr(cell_keys), _ptr(cell_start), U, _ptr(rank), _ptr(keep), _ptr(face_offset), _ptr(used),
+                                              _ptr(vertex_id), _ptr(faces_out), _ptr(pos), _ptr(nrm), _ptr(col_out), st))
+    return result(pos, faces_out, nrm, col_out)
 
 
 def kernel_timing_arm():

@@ -1,8 +1,11 @@
-"""`python extract_mesh.py <file.vol> [-o out.ply|out.obj] [--res N] [--iso v] [--albedo <file.vol> [--float-colors]]`: the triangle
+"""`python extract_mesh.py <file.vol> [-o out.ply|out.obj] [--res N] [--iso v] [--albedo <file.vol> [--float-colors]] [--simplify N]`: the triangle
 mesh of the surface the renderer sees in an SDF checkpoint (the `.vol` files optimize.py writes) -- dsdf.extract_mesh on util.read_vol,
 written by mesh_to_sdf.save_ply / save_obj with the vertex normals.  The mesh lives in the unit cube of the grid, like the SDF.
 --albedo: the reflectance checkpoint of a textured reconstruction (three channels); its value at every vertex is written as the vertex
-colour (linear, no gamma) -- uchar in a ply unless --float-colors."""
+colour (linear, no gamma) -- uchar in a ply unless --float-colors.
+--simplify N: the extracted mesh goes through dsdf.simplify_mesh at N cells along its longest extent before it is written (vertex
+clustering with quadric errors: a much lighter file whose surface stays where the full-resolution extraction put it); normals and
+colours are carried through."""
 import argparse
 import os
 import sys
@@ -20,8 +23,12 @@ def main(argv=None):
     ap.add_argument('--iso', type=float, default=0.0, help='level to extract (default 0)')
     ap.add_argument('--steps', type=int, default=24, help='bisection steps per vertex (1 ... 32)')
     ap.add_argument('--albedo', default=None, help='reflectance volume (three channels): baked onto the vertices as vertex colours')
+    ap.add_argument('--simplify', type=int, default=None, metavar='N',
+                    help='simplify the mesh by vertex clustering at N cells along its longest extent (dsdf.simplify_mesh)')
     ap.add_argument('--float-colors', action='store_true', help='ply: store the colours as float (lossless) instead of uchar')
     args = ap.parse_args(argv)
+    if args.simplify is not None and args.simplify < 1:
+        ap.error('--simplify needs a cell count >= 1')
     out = args.output or os.path.splitext(args.vol)[0] + '.ply'
     if not out.endswith(('.ply', '.obj')):
         ap.error('the output must be a .ply or an .obj file')
@@ -37,6 +44,11 @@ def main(argv=None):
         albedo = albedo.float().contiguous()
     v, f, n, *c = dsdf.extract_mesh(grid, resolution=args.res, iso=args.iso, steps=args.steps, colors=albedo)
     c = c[0] if c else None
+    if args.simplify is not None and f.shape[0] > 0:
+        full = f.shape[0]
+        v, f, n, *c = dsdf.simplify_mesh(v, f, args.simplify, normals=True, colors=c)
+        c = c[0] if c else None
+        print(f'simplified at {args.simplify} cells: {full} -> {f.shape[0]} faces')
     if out.endswith('.obj'):
         mesh_to_sdf.save_obj(out, v, f, n, colors=c)
     else:

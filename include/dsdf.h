@@ -529,6 +529,37 @@ int dsdf_iso_refine(const float *padded, int rx, int ry, int rz, const float *va
                     const int32_t *vert_edge, int64_t n_vert, int steps, float *positions /* V x 3 */, float *normals /* V x 3 or NULL */,
                     void *stream);
 
+/* ---- mesh simplification: vertex clustering with quadric error metrics (Lindstrom 2000; csrc/dsdf_simplify.h) ----
+ * An indexed mesh (vertices V x 3 float, faces F x 3 int32, every index in [0, V): the caller's duty) over a box lo / hi (HOST pointers,
+ * 3 floats each, lo < hi on every axis) cut into cx x cy x cz cells, cx cy cz < 2^31 (refused otherwise before any launch); 3 F < 2^31.
+ *   cell    of a vertex v, per axis: i = clamp(floor((v - lo) inv), 0, c - 1), inv = (float)c / (hi - lo) computed once on the host;
+ *           key = (iz cy + iy) cx + ix.  Every statement is rounded on its own (no FMA): a float32 numpy statement gives the same cell.
+ *   corner  3 f + k of face f.  A cell is OCCUPIED when a face corner lies in it; a face SURVIVES when its three cells differ; a cell is
+ *           USED when a surviving face has a corner in it.  Output vertices = the used cells in ascending key, output faces = the
+ *           survivors in input order with their winding kept (duplicates and opposite pairs are kept; non-manifold edges can appear).
+ * Sequence: dsdf_simplify_keys -> keys (3 F); the CALLER sorts them stably (plumbing, like the sort in front of dsdf_mesh_bvh_build):
+ * corner (3 F: the corner ids in sorted order), cell_keys (U: the distinct keys, ascending), cell_start (U + 1: the segment of cell r in
+ * `corner` is [cell_start[r], cell_start[r + 1])).  dsdf_simplify_mark -> rank (3 F: the index of every corner's cell in cell_keys),
+ * keep (F: 1 = survives) and used (U: the caller ZEROES it; 1 is stored for a used cell); the caller scans keep and used exclusively ->
+ * face_offset (F), vertex_id (U), and reads the two totals F', V' to allocate.  dsdf_simplify_emit -> faces_out (F' x 3),
+ * positions_out (V' x 3) and, unless NULL, normals_out (V' x 3: the normalised sum of N / 2 over the cell's records, 0 if it vanishes)
+ * and colors_out (V' x 3: the mean of `colors` (V x 3) over the cell's records).  The position of a used cell: one lane walks the cell's
+ * records in sorted order; with N = (p1 - p0) x (p2 - p0) of a record's face (|N| = 0: no quadric), n = N / |N|, a = |N| / 2,
+ * d = -n . (p0 - centre): A += a n n^T, b += a d n, area += a; m = the mean of the records' own corners; x minimises
+ * x^T A x + 2 b^T x + reg area |x - m|^2 (Cholesky; area = 0: x = m), clamped into the cell's box around its centre.  reg > 0
+ * (DSDF_SIMPLIFY_REG = 1e-3).  The arithmetic is uncontracted and correctly rounded: the device returns the bits of a host build.
+ * n_faces = 0 returns DSDF_OK without a launch (a bad grid is still refused).  Nothing here allocates or synchronises. */
+#define DSDF_SIMPLIFY_REG 1e-3f
+int dsdf_simplify_keys(const float *vertices, const int32_t *faces, int64_t n_faces, const float *lo, const float *hi, int cx, int cy, int cz,
+                       int32_t *keys_out /* 3 F */, void *stream);
+int dsdf_simplify_mark(const int32_t *keys, int64_t n_faces, const int32_t *cell_keys, int n_cells, int32_t *rank_out /* 3 F */,
+                       int32_t *keep_out /* F */, int32_t *used /* U, zeroed */, void *stream);
+int dsdf_simplify_emit(const float *vertices, const int32_t *faces, int64_t n_faces, const float *colors /* V x 3 or NULL */, const float *lo,
+                       const float *hi, int cx, int cy, int cz, float reg, const int32_t *corner, const int32_t *cell_keys,
+                       const int32_t *cell_start, int n_cells, const int32_t *rank, const int32_t *keep, const int32_t *face_offset,
+                       const int32_t *used, const int32_t *vertex_id, int32_t *faces_out, float *positions_out, float *normals_out,
+                       float *colors_out, void *stream);
+
 /* Trilinear lookup of a (vz, vy, vx, channels) fp32 volume on the unit cube, channels 1 or 3, at n points (n x 3, in the volume's frame):
  * out n x channels.  The value the direct integrator reads there (shading->albedo, ->roughness): texel centres (i + 0.5) / res, clamped
  * indices.  Bakes a reflectance volume onto the vertices of an extracted mesh (their WORLD-space positions: the volume lives in world
