@@ -2,7 +2,8 @@
 // on top of it (reference images of mesh scenes: python/optimize.py:11-40 renders them from the scene's mesh with Mitsuba).
 //
 // Two parts.  The first is host/device inline arithmetic (the triangle test, the slab test, the builder's per-element
-// statements, the stackless traversal) and compiles with any C++ compiler: the host-side tests run exactly these statements.
+// statements, the stackless traversal, what the loops over all triangles of dsdf_mesh.h keep per ray and per point, what a
+// closest-point query stores) and compiles with any C++ compiler: the host-side tests run exactly these statements.
 // The second, under __HIPCC__, holds the kernels and the C-ABI entry points and is included at the end of dsdf_kernels.hip.
 //
 // LAYOUT (ABI, include/dsdf.h).  An implicit COMPLETE binary tree in one caller-owned buffer of floats.  T triangles, 4 per
@@ -92,6 +93,16 @@ DSDF_HD bool tri_intersect(const float *p, V3 o, V3 d, TriHit &h) {
     const float t = dot_unfused(e2, qv) * inv;
     h.t = t; h.u = u; h.v = v; h.det = det;
     return u >= 0.f && v >= 0.f && u + v <= 1.f;
+}
+
+// What the loop over all triangles keeps of a ray (k_mesh_raycast, the host tests): the nearest hit beyond t_min.  Strict `<` in index
+// order, so the lowest index wins a tie -- the promise bvh_leaf keeps towards this loop.  back: det = e1 . (d x e2) = -d . (e1 x e2) is
+// negative when the normal points along the ray.
+struct RayBest { float t; int back, prim; };                        // prim: -1 = none, t = inf
+DSDF_HD void ray_best_init(RayBest &b) { b.t = INFINITY; b.back = 0; b.prim = -1; }
+DSDF_HD void ray_best_update(RayBest &b, const float *p, V3 o, V3 d, float t_min, int idx) {
+    TriHit h;
+    if (tri_intersect(p, o, d, h) && h.t > t_min && h.t < b.t) { b.t = h.t; b.back = h.det < 0.f ? 1 : 0; b.prim = idx; }
 }
 
 // ---- slab test ---------------------------------------------------------------------------------------------------------
@@ -358,6 +369,8 @@ DSDF_HD float box_dist2(const float *b, V3 x) {
 // 100 extents of the mesh; the tests stay inside 10.  Beyond that range the result is still the distance to some triangle, only
 // not necessarily the bits of the loop.
 struct BvhClosest { float d2; int prim, slot; float u, v; };        // prim: original triangle index, -1 = none within max_d2
+// every search -- the descent, the loop over all triangles -- starts from nothing found within the bound (closest_bound)
+DSDF_HD void closest_init(BvhClosest &r, float max_d2) { r.d2 = max_d2; r.prim = -1; r.slot = 0; r.u = 0.f; r.v = 0.f; }
 // closed at the starting bound, and on equal d2 the lower original index wins: what `<` gives a loop in index order
 DSDF_HD void closest_update(BvhClosest &r, const TriClosest &c, int idx, int s) {
     if ((c.d2 < r.d2 || (c.d2 == r.d2 && (r.prim < 0 || idx < r.prim))) && c.d2 < INFINITY) { r.d2 = c.d2; r.prim = idx; r.slot = s; r.u = c.u; r.v = c.v; }
@@ -379,7 +392,7 @@ DSDF_HD void bvh_closest_leaf(const BvhView &B, int j, V3 x, BvhClosest &r) {
 // at exactly the best distance with a lower index still wins) and finite.
 template <class Nodes>
 DSDF_HD void bvh_closest(const BvhView &B, const Nodes &N, V3 x, float max_d2, BvhClosest &r) {
-    r.d2 = max_d2; r.prim = -1; r.slot = 0; r.u = 0.f; r.v = 0.f;
+    closest_init(r, max_d2);
     const uint32_t inner = (uint32_t)B.L - 1u;
     if (inner == 0u) { bvh_closest_leaf(B, 0, x, r); return; }
     uint32_t i = 0;
@@ -420,6 +433,19 @@ DSDF_HD float closest_dist(BvhClosest &r, float max_dist) {
     if (r.prim >= 0 && d <= max_dist) return d;
     r.prim = -1;
     return INFINITY;
+}
+// what every closest-point query -- both kernels, the host tests -- writes for point i from the search result and the nine floats of the
+// winning triangle; every output but the distance may be null
+DSDF_HD void closest_store(BvhClosest r, const float *p, float max_dist, int64_t i, float *__restrict__ dist_out, int32_t *__restrict__ prim_out,
+                           float *__restrict__ point_out, float *__restrict__ bary_out) {
+    dist_out[i] = closest_dist(r, max_dist);
+    if (prim_out) prim_out[i] = r.prim;
+    const bool found = r.prim >= 0;
+    if (point_out) {
+        const V3 q = found ? tri_point(p, r.u, r.v) : mk(0.f, 0.f, 0.f);
+        point_out[3 * i] = q.x; point_out[3 * i + 1] = q.y; point_out[3 * i + 2] = q.z;
+    }
+    if (bary_out) { bary_out[2 * i] = found ? r.u : 0.f; bary_out[2 * i + 1] = found ? r.v : 0.f; }
 }
 
 // the shading normal of a hit: the interpolated vertex normals when the buffer has them, else the geometric normal
@@ -506,19 +532,6 @@ __global__ __launch_bounds__(256) void k_mesh_bvh_raycast(const float *__restric
     t_out[i] = h.t;
     if (back_out) back_out[i] = (h.prim >= 0 && h.det < 0.f) ? 1 : 0;
     if (prim_out) prim_out[i] = h.prim;
-}
-
-// what both closest-point kernels write for point i from the search result and the nine floats of the winning triangle
-__device__ __forceinline__ void closest_store(BvhClosest r, const float *p, float max_dist, int64_t i, float *__restrict__ dist_out,
-                                              int32_t *__restrict__ prim_out, float *__restrict__ point_out, float *__restrict__ bary_out) {
-    dist_out[i] = closest_dist(r, max_dist);
-    if (prim_out) prim_out[i] = r.prim;
-    const bool found = r.prim >= 0;
-    if (point_out) {
-        const V3 q = found ? tri_point(p, r.u, r.v) : mk(0.f, 0.f, 0.f);
-        point_out[3 * i] = q.x; point_out[3 * i + 1] = q.y; point_out[3 * i + 2] = q.z;
-    }
-    if (bary_out) { bary_out[2 * i] = found ? r.u : 0.f; bary_out[2 * i + 1] = found ? r.v : 0.f; }
 }
 
 // one lane per query point
@@ -656,9 +669,9 @@ int dsdf_mesh_bvh_build(const float *triangles, const float *normals, const int3
     const int L = bvh_leaves(n_triangles);
     int rc;
     if ((rc = launch("k_bvh_header", k_bvh_header, dim3(1), dim3(1024), st, triangles, n_triangles, normals ? 1 : 0, bvh))) return rc;
-    if ((rc = launch("k_bvh_leaves", k_bvh_leaves, dim3((unsigned)((L + 255) / 256)), dim3(256), st, bvh, triangles, normals, order, L))) return rc;
+    if ((rc = launch_lanes("k_bvh_leaves", k_bvh_leaves, L, st, bvh, triangles, normals, order, L))) return rc;
     for (uint32_t count = (uint32_t)L >> 1; count >= 2; count >>= 1)       // nodes [count - 1, 2 count - 1): the level above the last fitted one
-        if ((rc = launch("k_bvh_level", k_bvh_level, dim3((count + 255) / 256), dim3(256), st, bvh, count - 1u, count))) return rc;
+        if ((rc = launch_lanes("k_bvh_level", k_bvh_level, count, st, bvh, count - 1u, count))) return rc;
     return DSDF_OK;
 }
 
@@ -666,7 +679,7 @@ int dsdf_mesh_bvh_raycast(const float *bvh, const float *rays_o, const float *ra
                           int32_t *backface_out, int32_t *prim_out, void *stream) {
     if (n == 0) return DSDF_OK;
     if (!bvh || !rays_o || !rays_d || !t_out || n < 0) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_raycast: bad argument");
-    return launch("k_mesh_bvh_raycast", k_mesh_bvh_raycast, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, bvh, rays_o,
+    return launch_lanes("k_mesh_bvh_raycast", k_mesh_bvh_raycast, n, (hipStream_t)stream, bvh, rays_o,
                   rays_d, n, t_min, t_out, backface_out, prim_out);
 }
 
@@ -674,7 +687,7 @@ int dsdf_mesh_bvh_closest(const float *bvh, const float *points, int64_t n, floa
                           float *point_out, float *bary_out, void *stream) {
     if (n == 0) return DSDF_OK;
     if (!bvh || !points || !dist_out || n < 0 || !(max_dist >= 0.f)) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_closest: bad argument");
-    return launch("k_mesh_bvh_closest", k_mesh_bvh_closest, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, bvh, points, n,
+    return launch_lanes("k_mesh_bvh_closest", k_mesh_bvh_closest, n, (hipStream_t)stream, bvh, points, n,
                   max_dist, dist_out, prim_out, point_out, bary_out);
 }
 

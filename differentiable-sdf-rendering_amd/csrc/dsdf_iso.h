@@ -283,7 +283,7 @@ int dsdf_iso_sample(const float *padded, int rx, int ry, int rz, int nx, int ny,
     if (rx < 1 || ry < 1 || rz < 1) return fail(DSDF_ERR_INVALID_ARG, "dsdf_iso_sample: bad grid size");
     if (int rc = iso_check_lattice("dsdf_iso_sample", nx, ny, nz)) return rc;
     const int n = (int)iso_node_count(nx, ny, nz);
-    return launch("k_iso_sample", k_iso_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, iso_view(padded, rx, ry, rz),
+    return launch_lanes("k_iso_sample", k_iso_sample, n, (hipStream_t)stream, iso_view(padded, rx, ry, rz),
                   iso_lattice(nx, ny, nz), n, values);
 }
 
@@ -291,7 +291,7 @@ int dsdf_iso_mark(const float *values, int nx, int ny, int nz, float iso, uint8_
     if (!values || !cross || !n_vert || !n_tri) return fail(DSDF_ERR_INVALID_ARG, "dsdf_iso_mark: null pointer argument");
     if (int rc = iso_check_lattice("dsdf_iso_mark", nx, ny, nz)) return rc;
     const int n = (int)iso_node_count(nx, ny, nz);
-    return launch("k_iso_mark", k_iso_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, iso_lattice(nx, ny, nz), n, values, iso,
+    return launch_lanes("k_iso_mark", k_iso_mark, n, (hipStream_t)stream, iso_lattice(nx, ny, nz), n, values, iso,
                   cross, n_vert, n_tri);
 }
 
@@ -302,7 +302,7 @@ int dsdf_iso_emit(const float *values, int nx, int ny, int nz, float iso, const 
     if (int rc = iso_check_lattice("dsdf_iso_emit", nx, ny, nz)) return rc;
     if (!vert_edge) return DSDF_OK;                // no vertex, hence no face
     const int n = (int)iso_node_count(nx, ny, nz);
-    return launch("k_iso_emit", k_iso_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, iso_lattice(nx, ny, nz), n, values, iso,
+    return launch_lanes("k_iso_emit", k_iso_emit, n, (hipStream_t)stream, iso_lattice(nx, ny, nz), n, values, iso,
                   cross, vert_offset, tri_offset, vert_edge, faces);
 }
 
@@ -315,7 +315,7 @@ int dsdf_iso_refine(const float *padded, int rx, int ry, int rz, const float *va
     if (n_vert == 0) return DSDF_OK;
     if (!padded || !values || !vert_edge || !positions) return fail(DSDF_ERR_INVALID_ARG, "dsdf_iso_refine: null pointer argument");
     if (n_vert > 7 * iso_node_count(nx, ny, nz)) return fail(DSDF_ERR_INVALID_ARG, "dsdf_iso_refine: more vertices than the lattice has edges");
-    return launch("k_iso_refine", k_iso_refine, dim3((unsigned)((n_vert + 255) / 256)), dim3(256), (hipStream_t)stream, iso_view(padded, rx, ry, rz),
+    return launch_lanes("k_iso_refine", k_iso_refine, n_vert, (hipStream_t)stream, iso_view(padded, rx, ry, rz),
                   iso_lattice(nx, ny, nz), values, iso, vert_edge, n_vert, steps, positions, normals);
 }
 
@@ -328,7 +328,7 @@ int dsdf_volume_sample(const float *volume, int vx, int vy, int vz, int channels
     if (!points || !out) return fail(DSDF_ERR_INVALID_ARG, "dsdf_volume_sample: null pointer argument");
     AlbedoView A;
     A.data = volume; A.rx = vx; A.ry = vy; A.rz = vz;
-    return launch("k_volume_sample", k_volume_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, A, channels, points, n, out);
+    return launch_lanes("k_volume_sample", k_volume_sample, n, (hipStream_t)stream, A, channels, points, n, out);
 }
 
 }  // extern "C"

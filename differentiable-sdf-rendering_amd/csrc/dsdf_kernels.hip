@@ -944,6 +944,11 @@ static int launch(const char *what, void (*k)(P...), dim3 grid, dim3 block, hipS
     hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(args)...);
     return check_launch(what);
 }
+// one lane per element: n elements in blocks of 256 threads
+template <class... P, class... A>
+static int launch_lanes(const char *what, void (*k)(P...), int64_t n, hipStream_t st, A &&...args) {
+    return launch(what, k, dim3((unsigned)((n + 255) / 256)), dim3(256), st, args...);
+}
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -201,7 +201,7 @@ int dsdf_simplify_keys(const float *vertices, const int32_t *faces, int64_t n_fa
     if (!vertices || !faces || !keys_out || n_faces < 0 || n_faces > (int64_t)0x7fffffff / 3)
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_simplify_keys: bad argument (null pointer, or 3 n_faces >= 2^31)");
     const int64_t n = 3 * n_faces;
-    return launch("k_simplify_keys", k_simplify_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, G, vertices, faces, n, keys_out);
+    return launch_lanes("k_simplify_keys", k_simplify_keys, n, (hipStream_t)stream, G, vertices, faces, n, keys_out);
 }
 
 int dsdf_simplify_mark(const int32_t *keys, int64_t n_faces, const int32_t *cell_keys, int n_cells, int32_t *rank_out, int32_t *keep_out,
@@ -209,7 +209,7 @@ int dsdf_simplify_mark(const int32_t *keys, int64_t n_faces, const int32_t *cell
     if (n_faces == 0) return DSDF_OK;
     if (!keys || !cell_keys || !rank_out || !keep_out || !used || n_faces < 0 || n_faces > (int64_t)0x7fffffff / 3 || n_cells < 1)
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_simplify_mark: bad argument");
-    return launch("k_simplify_mark", k_simplify_mark, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), (hipStream_t)stream, keys, n_faces, cell_keys,
+    return launch_lanes("k_simplify_mark", k_simplify_mark, n_faces, (hipStream_t)stream, keys, n_faces, cell_keys,
                   n_cells, rank_out, keep_out, used);
 }
 
@@ -227,7 +227,7 @@ int dsdf_simplify_emit(const float *vertices, const int32_t *faces, int64_t n_fa
         return fail(DSDF_ERR_INVALID_ARG, "dsdf_simplify_emit: bad argument");
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = launch("k_simplify_faces", k_simplify_faces, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), st, rank, keep, face_offset, vertex_id, n_faces,
+    if ((rc = launch_lanes("k_simplify_faces", k_simplify_faces, n_faces, st, rank, keep, face_offset, vertex_id, n_faces,
                      faces_out))) return rc;
     return launch("k_simplify_cells", k_simplify_cells, dim3((unsigned)((n_cells + 63) / 64)), dim3(64), st, G, reg, vertices, faces, colors, corner, cell_keys,
                   cell_start, n_cells, used, vertex_id, positions_out, normals_out, colors_out);

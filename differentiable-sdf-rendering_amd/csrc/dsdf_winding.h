@@ -192,12 +192,12 @@ DSDF_HD float bvh_winding(const BvhView &B, const float *mom, V3 x, float beta) 
 
 #if defined(__HIPCC__)
 // =========================================================================================================================
-// Kernels and entry points (fail / launch of dsdf_kernels.hip and DSDF_MESH_TILE of dsdf_mesh.h are in scope).
+// Kernels and entry points (fail / launch of dsdf_kernels.hip and the tile loop of dsdf_mesh.h are in scope).
 // =========================================================================================================================
 
-// The exact sum, N-body style like k_mesh_closest: a block stages DSDF_MESH_TILE triangles in LDS (read as broadcasts) and every thread
-// adds their solid angles at its point, in index order.  atan2f is the expensive instruction of the inner loop (~40 VALU instructions of
-// its own against ~45 for the rest of the term).
+// The exact sum, N-body style like k_mesh_closest (mesh_for_each_triangle, dsdf_mesh.h): every thread adds the solid angles of the staged
+// triangles at its point, in index order.  atan2f is the expensive instruction of the inner loop (~40 VALU instructions of its own
+// against ~45 for the rest of the term).
 __global__ __launch_bounds__(256) void k_mesh_winding(const float *__restrict__ tri, int n_tri, const float *__restrict__ pts, int64_t n,
                                                       float *__restrict__ w_out) {
     __shared__ float tile[DSDF_MESH_TILE * 9];
@@ -206,13 +206,7 @@ __global__ __launch_bounds__(256) void k_mesh_winding(const float *__restrict__ 
     V3 x = mk(0.f, 0.f, 0.f);
     if (on) x = mk(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
     float s = 0.f;
-    for (int t0 = 0; t0 < n_tri; t0 += DSDF_MESH_TILE) {
-        const int cnt = min(DSDF_MESH_TILE, n_tri - t0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < cnt * 9; e += blockDim.x) tile[e] = tri[(size_t)t0 * 9 + e];
-        __syncthreads();
-        for (int k = 0; k < cnt; ++k) s += tri_solid_angle(tile + k * 9, x);
-    }
+    mesh_for_each_triangle(tri, n_tri, tile, [&s, x](const float *p, int) { s += tri_solid_angle(p, x); });
     if (on) w_out[i] = s * DSDF_WIND_INV_4PI;
 }
 
@@ -243,7 +237,7 @@ extern "C" {
 int dsdf_mesh_winding(const float *triangles, int n_triangles, const float *points, int64_t n, float *w_out, void *stream) {
     if (n == 0) return DSDF_OK;
     if (!triangles || n_triangles < 1 || !points || !w_out || n < 0) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_winding: bad argument");
-    return launch("k_mesh_winding", k_mesh_winding, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, triangles, n_triangles,
+    return launch_lanes("k_mesh_winding", k_mesh_winding, n, (hipStream_t)stream, triangles, n_triangles,
                   points, n, w_out);
 }
 
@@ -254,9 +248,9 @@ int dsdf_mesh_bvh_moments(const float *bvh, int n_triangles, float *moments_out,
     hipStream_t st = (hipStream_t)stream;
     const int L = bvh_leaves(n_triangles);
     int rc;
-    if ((rc = launch("k_wind_leaves", k_wind_leaves, dim3((unsigned)((L + 255) / 256)), dim3(256), st, bvh, moments_out, L))) return rc;
+    if ((rc = launch_lanes("k_wind_leaves", k_wind_leaves, L, st, bvh, moments_out, L))) return rc;
     for (uint32_t count = (uint32_t)L >> 1; count >= 1; count >>= 1)       // nodes [count - 1, 2 count - 1), the root included
-        if ((rc = launch("k_wind_level", k_wind_level, dim3((count + 255) / 256), dim3(256), st, moments_out, count - 1u, count))) return rc;
+        if ((rc = launch_lanes("k_wind_level", k_wind_level, count, st, moments_out, count - 1u, count))) return rc;
     return DSDF_OK;
 }
 
@@ -264,7 +258,7 @@ int dsdf_mesh_bvh_winding(const float *bvh, const float *moments, const float *p
     if (n == 0) return DSDF_OK;
     if (!bvh || !moments || !points || !w_out || n < 0) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_winding: bad argument");
     if (!(beta >= 1.f)) return fail(DSDF_ERR_INVALID_ARG, "dsdf_mesh_bvh_winding: beta must be >= 1 (+inf: the exact sum)");
-    return launch("k_mesh_bvh_winding", k_mesh_bvh_winding, dim3((unsigned)((n + 255) / 256)), dim3(256), (hipStream_t)stream, bvh, moments,
+    return launch_lanes("k_mesh_bvh_winding", k_mesh_bvh_winding, n, (hipStream_t)stream, bvh, moments,
                   points, n, beta, w_out);
 }
 

@@ -1,13 +1,10 @@
 // TEST-ONLY host build of the winding-number arithmetic (csrc/dsdf_winding.h): tri_solid_angle, the per-node moments and the stackless
-// walk bvh_winding, run serially on the CPU next to the loop over all triangles that k_mesh_winding runs.  The CPU test-suite compares
-// them with an fp64 reference in another formulation; `main` runs a case file and serves the sanitizer build.  It is NOT a fallback: the
-// product only ever loads the HIP library.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <numeric>
-#include <vector>
+// walk bvh_winding, run serially on the CPU next to the loop over all triangles that k_mesh_winding runs (the sum of tri_solid_angle in
+// index order); the tree is built by dsdf_mesh_host.h.  The CPU test-suite compares them with an fp64 reference in another formulation;
+// `main` runs a case file and serves the sanitizer build.  It is NOT a fallback: the product only ever loads the HIP library.
+#include <cmath>
 #include "../../differentiable-sdf-rendering_amd/csrc/dsdf_winding.h"
+#include "dsdf_mesh_host.h"
 
 using namespace dsdf;
 
@@ -19,23 +16,10 @@ long winding_host_moments_size(int n_tri) { return (long)winding_moment_floats(n
 // the library's two builds (dsdf_mesh_bvh_build, dsdf_mesh_bvh_moments), serially; order = NULL: Morton order of the centroids, ties in
 // index order
 void winding_host_build(const float *tri, const int32_t *order, int n_tri, float *bvh, float *mom) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (long e = 0; e < (long)n_tri * 3; ++e)
-        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], tri[3 * e + a]); hi[a] = fmaxf(hi[a], tri[3 * e + a]); }
     std::vector<int32_t> morton;
-    if (!order) {
-        std::vector<int32_t> codes(n_tri);
-        for (int t = 0; t < n_tri; ++t) codes[t] = bvh_morton(tri + (size_t)9 * t, lo, hi);
-        morton.resize(n_tri);
-        std::iota(morton.begin(), morton.end(), 0);
-        std::stable_sort(morton.begin(), morton.end(), [&](int32_t a, int32_t b) { return codes[a] < codes[b]; });
-        order = morton.data();
-    }
-    bvh_write_header(bvh, n_tri, 0, lo, hi);
+    if (!order) { morton = host_morton_order(tri, n_tri); order = morton.data(); }
+    host_bvh_build(tri, nullptr, order, n_tri, bvh);
     const int L = bvh_leaves(n_tri);
-    for (int j = 0; j < L; ++j) bvh_write_leaf(bvh, tri, nullptr, order, j);
-    for (uint32_t count = (uint32_t)L >> 1; count >= 2; count >>= 1)
-        for (uint32_t k = 0; k < count; ++k) bvh_fit_node(bvh, count - 1u + k);
     for (int j = 0; j < L; ++j) winding_leaf_moments(bvh, mom, j);
     for (uint32_t count = (uint32_t)L >> 1; count >= 1; count >>= 1)
         for (uint32_t k = 0; k < count; ++k) winding_node_moments(mom, count - 1u + k);
@@ -70,15 +54,11 @@ void winding_host_tri(const float *tri, const float *pts, long n, float *omega) 
 // Morton order, walks both at beta = inf and at beta, and compares with the loop over all triangles: the exact walk adds the same terms in
 // another order (1e-4 covers that), every result of a finite point is finite; exit status 1 on a mismatch.
 int main(int argc, char **argv) {
-    if (argc < 2) { fprintf(stderr, "usage: %s case.bin\n", argv[0]); return 2; }
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) { perror(argv[1]); return 2; }
-    int32_t T = 0, n = 0;
-    float beta = 0.f;
-    if (fread(&T, 4, 1, f) != 1 || fread(&n, 4, 1, f) != 1 || fread(&beta, 4, 1, f) != 1 || T < 1 || n < 0) { fprintf(stderr, "bad header\n"); return 2; }
-    std::vector<float> tri((size_t)9 * T), pts((size_t)3 * n);
-    if (fread(tri.data(), 4, tri.size(), f) != tri.size() || fread(pts.data(), 4, pts.size(), f) != pts.size()) { fprintf(stderr, "truncated case file\n"); return 2; }
-    fclose(f);
+    HostCase c;
+    if (int rc = host_read_case(argc, argv, 1, c)) return rc;
+    const int T = c.T, n = c.n;
+    const float beta = c.scalar;
+    const std::vector<float> &tri = c.tri, &pts = c.blocks[0];
     std::vector<float> w0(n), w1(n), w2(n);
     std::vector<int32_t> given(T);
     std::iota(given.begin(), given.end(), 0);

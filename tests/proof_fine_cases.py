@@ -4,16 +4,12 @@ empty-space proof and of the third proof stage (tests/harness/dsdf_proof_stages_
 library and constants)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import sdf_oracle as O
+from host_build import ptr as _p, shared_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_proof_stages_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
 CASES = ['sphere64', 'blob64_flat', 'rag_x3']
 PX_EMPTY, PX_EMPTY_G, PX_HIT, PX_EMPTY_FINE = 1, 2, 16, 128
 PX_KEEP = PX_EMPTY | PX_EMPTY_G | PX_HIT | PX_EMPTY_FINE
@@ -22,18 +18,9 @@ ICAM, NCAM = 2, 5
 
 @functools.lru_cache(None)
 def host_lib():
-    os.makedirs(OUT, exist_ok=True)
-    out = os.path.join(OUT, 'libdsdf_proof_stages_host.so')
-    r = subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True)
-    assert r.returncode == 0, r.stdout
-    lib = C.CDLL(out)
+    lib = shared_lib('dsdf_proof_stages_host.cpp')
     lib.psh_fine_empty.restype = lib.psh_proofs.restype = C.c_float
     return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @functools.lru_cache(None)

@@ -4,34 +4,21 @@ ray and the one restricted to the stretch near the shape (csrc/dsdf_proof.h: pro
 that are built to go wrong: a surface on the box faces, a slab two voxels thick, a ragged noise grid."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import sdf_oracle as O
+from host_build import ptr as _p, shared_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_proof_interval_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
 COUNTERS = ['round', 'light', 'leap', 'bmin', 'bmax', 'value', 'walk']      # csrc/dsdf_proof.h: DSDF_PC_*
 NOISE_SHAPE = (17, 16, 33)
 
 
 @functools.lru_cache(None)
 def host_lib():
-    os.makedirs(OUT, exist_ok=True)
-    out = os.path.join(OUT, 'libdsdf_proof_interval_host.so')
-    r = subprocess.run(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True)
-    assert r.returncode == 0, r.stdout
-    lib = C.CDLL(out)
+    lib = shared_lib('dsdf_proof_interval_host.cpp')
     lib.psi_proofs.restype = lib.psi_certificate.restype = C.c_float
     return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _axes(shape):

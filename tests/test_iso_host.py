@@ -3,33 +3,18 @@ runs the per-node and per-vertex statements of the four kernels serially, agains
 EQUAL to the oracle's on the same value buffer, vertices on the rendered surface to fp32 noise of the lookup, orientation, second-order
 convergence; the mesh writers; the argument checks of the four entry points of the built library."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import iso_cases as I
+from host_build import compile as compile_host, ptr as _p, run_case, sanitized_program, shared_lib
 from iso_cases import ON_EDGE_TOL, VERTEX_RESIDUAL_GATE, assert_same_topology
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_iso_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
-
-def _compile(out, flags):
-    os.makedirs(OUT, exist_ok=True)
-    r = subprocess.run(['g++', '-O2', '-std=c++17'] + flags + ['-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return out
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 class Host:
-    def __init__(self, path):
-        self.lib = C.CDLL(path)
+    def __init__(self, lib):
+        self.lib = lib
         self._meshes = {}
 
     def sample(self, data, n, sdf_p=None):
@@ -71,7 +56,7 @@ class Host:
 
 @pytest.fixture(scope='module')
 def host():
-    return Host(_compile(os.path.join(OUT, 'libdsdf_iso_host.so'), ['-shared', '-fPIC']))
+    return Host(shared_lib('dsdf_iso_host.cpp'))
 
 
 def test_case_table_against_the_geometric_rule(host):
@@ -175,7 +160,7 @@ def test_frame_is_the_cubes_own(host):
     n = (16, 16, 16)
     m = host.mesh('sphere16', n)
     assert np.array_equal(host.sample(I.grid('sphere16'), n, sdf_p=(0.25, -0.5, 0.125)), m['values'])
-    xf = Host(_compile(os.path.join(OUT, 'libdsdf_iso_host_xf.so'), ['-shared', '-fPIC', '-DDSDF_XF=1']))
+    xf = Host(C.CDLL(compile_host('dsdf_iso_host.cpp', 'libdsdf_iso_host_xf.so', ['-shared', '-fPIC', '-DDSDF_XF=1'])))
     assert xf.lib.iso_host_xf() == 1 and host.lib.iso_host_xf() == 0
     c, s = np.cos(0.3), np.sin(0.3)
     to_local = np.array([[1.5 * c, -s, 0, 0.1], [s, 0.8 * c, 0, -0.2], [0, 0, 1.25, 0.05]], np.float32)
@@ -262,7 +247,7 @@ def _case_file(path, n, values, ref, iso=0.0, data=None):
 def test_standalone_program_under_sanitizers(host, tmp_path):
     """(h) the stand-alone program (its own main, nothing loaded into Python) built with AddressSanitizer + UBSan runs (a) clean: every
     value lattice, and every grid with its sampling and its vertices."""
-    exe = _compile(os.path.join(OUT, 'dsdf_iso_host_asan'), ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined'])
+    exe = sanitized_program('dsdf_iso_host.cpp')
     files = []
     for name, (n, values) in I.VALUE_LATTICES.items():
         files.append(_case_file(tmp_path / f'{name}.bin', n, values, I.topology(values, n)))
@@ -270,6 +255,4 @@ def test_standalone_program_under_sanitizers(host, tmp_path):
         m = host.mesh(name, n)
         files.append(_case_file(tmp_path / f'{name}.bin', n, m['values'], I.topology(m['values'], n), data=I.grid(name)))
     for fn in files:
-        r = subprocess.run([exe, fn], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, (fn, r.stdout)
-        assert ' 0 mismatches' in r.stdout and 'runtime error' not in r.stdout and 'AddressSanitizer' not in r.stdout, (fn, r.stdout)
+        run_case(exe, fn)

@@ -3,35 +3,17 @@ traversal must return BITWISE the same t, back-face flag and primitive index as 
 function -- on buffers written by a numpy builder from the layout documented in include/dsdf.h, and on buffers written by the
 library's own per-element build statements run serially."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_build import ptr as _p, run_case, sanitized_program, shared_lib
 from mesh_bvh_cases import MESHES, morton_order, n_leaves, numpy_bvh, ray_sets
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_bvh_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
-
-
-def _compile(out, flags):
-    os.makedirs(OUT, exist_ok=True)
-    r = subprocess.run(['g++', '-O2', '-std=c++17'] + flags + ['-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return out
 
 
 @pytest.fixture(scope='module')
 def host():
-    lib = C.CDLL(_compile(os.path.join(OUT, 'libdsdf_bvh_host.so'), ['-shared', '-fPIC']))
-    lib.bvh_host_size.restype = C.c_long
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return shared_lib('dsdf_bvh_host.cpp', long_returning=['bvh_host_size'])
 
 
 def cast_both(host, buf, tri, o, d, t_min):
@@ -91,7 +73,7 @@ def test_given_order_and_anyhit(host):
 
 def test_standalone_program_under_sanitizers(tmp_path):
     """The stand-alone program (its own main, nothing loaded into Python) built with AddressSanitizer + UBSan, on the 320-triangle case."""
-    exe = _compile(os.path.join(OUT, 'dsdf_bvh_host_asan'), ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined'])
+    exe = sanitized_program('dsdf_bvh_host.cpp')
     tri = MESHES['ico320']
     sets = ray_sets(tri, 6)
     o = np.concatenate([sets[k][0] for k in ('random', 'axis', 'inside', 'miss_root')])
@@ -100,6 +82,4 @@ def test_standalone_program_under_sanitizers(tmp_path):
     with open(fn, 'wb') as fh:
         fh.write(np.asarray([tri.shape[0], o.shape[0]], np.int32).tobytes() + np.float32(0.0).tobytes())
         fh.write(tri.tobytes() + o.tobytes() + d.tobytes())
-    r = subprocess.run([exe, str(fn)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    assert ' 0 mismatches' in r.stdout and 'runtime error' not in r.stdout and 'AddressSanitizer' not in r.stdout, r.stdout
+    run_case(exe, fn)

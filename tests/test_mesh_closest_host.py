@@ -8,42 +8,24 @@ distance is 4.8e-07; 1.9e-07 on the points in [-1, 1]^3); the gate is 4 x that, 
 other arithmetic; mesh_closest_oracle.GATE, shared with the GPU tests).  `PYTHONPATH=oracle:tests python tests/test_mesh_closest_host.py`
 prints the measurement."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mesh_closest_oracle as O
+from host_build import ptr as _p, run_case, sanitized_program, shared_lib
 from mesh_bvh_cases import morton_order, n_leaves
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_closest_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
 
 GATE = O.GATE
 
 
-def _compile(out, flags):
-    os.makedirs(OUT, exist_ok=True)
-    r = subprocess.run(['g++', '-O2', '-std=c++17'] + flags + ['-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return out
-
-
 def load_host():
-    lib = C.CDLL(_compile(os.path.join(OUT, 'libdsdf_closest_host.so'), ['-shared', '-fPIC']))
-    lib.closest_host_size.restype = C.c_long
-    return lib
+    return shared_lib('dsdf_closest_host.cpp', long_returning=['closest_host_size'])
 
 
 @pytest.fixture(scope='module')
 def host():
     return load_host()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def build(host, tri, order):
@@ -169,7 +151,7 @@ def test_nan_point_terminates(host):
 def test_standalone_program_under_sanitizers(tmp_path):
     """The stand-alone program (its own main, nothing loaded into Python) built with AddressSanitizer + UBSan: the same meshes and
     points, a NaN point among them, without and with a limit."""
-    exe = _compile(os.path.join(OUT, 'dsdf_closest_host_asan'), ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined'])
+    exe = sanitized_program('dsdf_closest_host.cpp')
     for name, tri in O.MESHES.items():
         pts = np.concatenate([O.all_points(tri, len(name), n_random=2000), np.float32([[np.nan, 0, 0]])])
         for max_dist in (np.inf, 0.3):
@@ -177,9 +159,7 @@ def test_standalone_program_under_sanitizers(tmp_path):
             with open(fn, 'wb') as fh:
                 fh.write(np.asarray([tri.shape[0], pts.shape[0]], np.int32).tobytes() + np.float32(max_dist).tobytes())
                 fh.write(tri.tobytes() + pts.tobytes())
-            r = subprocess.run([exe, str(fn)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            assert r.returncode == 0, r.stdout
-            assert ' 0 mismatches' in r.stdout and 'runtime error' not in r.stdout and 'AddressSanitizer' not in r.stdout, r.stdout
+            run_case(exe, fn)
 
 
 def test_python_layer_checks_that_need_no_device(tmp_path):

@@ -10,8 +10,6 @@ its corners moved inside their cells).  2: on a closed mesh the winding number o
 point farther than D from the input surface.  3: in a cell that holds a corner of the cube the representative lies within 0.01 D of it.
 `PYTHONPATH=oracle:tests python tests/test_mesh_simplify_host.py` prints the measurements (profiles/mesh_simplify.md holds them)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,34 +17,18 @@ import pytest
 import mesh_closest_oracle as CO
 import mesh_simplify_oracle as O
 import mesh_winding_oracle as WO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_simplify_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
+from host_build import ptr as _p, run_case, sanitized_program, shared_lib
 
 GATE = O.GATE
 
 
-def _compile(out, flags):
-    os.makedirs(OUT, exist_ok=True)
-    r = subprocess.run(['g++', '-O2', '-std=c++17'] + flags + ['-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return out
-
-
 def load_host():
-    lib = C.CDLL(_compile(os.path.join(OUT, 'libdsdf_simplify_host.so'), ['-shared', '-fPIC']))
-    lib.simplify_host.restype = C.c_int
-    return lib
+    return shared_lib('dsdf_simplify_host.cpp')
 
 
 @pytest.fixture(scope='module')
 def host():
     return load_host()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def simplify(host, v, f, lo, hi, cells, reg=O.REG, colors=None, normals=True):
@@ -237,7 +219,7 @@ def test_no_faces_and_refusals(host):
 def test_standalone_program_under_sanitizers(tmp_path):
     """The stand-alone program (its own main, nothing loaded into Python) built with AddressSanitizer + UBSan over every mesh of the table,
     and over one with a NaN and an infinite vertex."""
-    exe = _compile(os.path.join(OUT, 'dsdf_simplify_host_asan'), ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined'])
+    exe = sanitized_program('dsdf_simplify_host.cpp')
     runs = [(n,) + O.mesh(m) + (b, c) for n, (m, b, c) in O.CASES.items()]
     v, f = O.mesh('sphere')
     v = v.copy()
@@ -248,9 +230,7 @@ def test_standalone_program_under_sanitizers(tmp_path):
         with open(fn, 'wb') as fh:
             fh.write(np.asarray([len(v), len(f)] + list(cells), np.int32).tobytes() + np.asarray(lo + hi, np.float32).tobytes())
             fh.write(np.ascontiguousarray(v, np.float32).tobytes() + np.nan_to_num(O.colors_of(v)).tobytes() + np.ascontiguousarray(f, np.int32).tobytes())
-        r = subprocess.run([exe, str(fn)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, (name, r.stdout)
-        assert ' 0 failures' in r.stdout and 'runtime error' not in r.stdout and 'AddressSanitizer' not in r.stdout, r.stdout
+        run_case(exe, fn, verdict=' 0 failures')
 
 
 def test_python_layer_checks_that_need_no_device():

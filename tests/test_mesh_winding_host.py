@@ -9,44 +9,25 @@ the walk stays within 0.1 of the fp64 exact sum on every mesh, and the error at 
 the fp32 rounding of the sum itself, GATE -- on a tree of one leaf every beta gives the same exact sum).
 `PYTHONPATH=oracle:tests python tests/test_mesh_winding_host.py` prints the measurements (profiles/mesh_winding.md holds them)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mesh_closest_oracle as CO
 import mesh_winding_oracle as O
+from host_build import ptr as _p, run_case, sanitized_program, shared_lib
 from mesh_bvh_cases import morton_order, n_leaves
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'tests', 'harness', 'dsdf_winding_host.cpp')
-OUT = os.path.join(ROOT, 'tests', 'harness', '_build')
 
 GATE = O.GATE
 
 
-def _compile(out, flags):
-    os.makedirs(OUT, exist_ok=True)
-    r = subprocess.run(['g++', '-O2', '-std=c++17'] + flags + ['-o', out, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return out
-
-
 def load_host():
-    lib = C.CDLL(_compile(os.path.join(OUT, 'libdsdf_winding_host.so'), ['-shared', '-fPIC']))
-    lib.winding_host_size.restype = C.c_long
-    lib.winding_host_moments_size.restype = C.c_long
-    return lib
+    return shared_lib('dsdf_winding_host.cpp', long_returning=['winding_host_size', 'winding_host_moments_size'])
 
 
 @pytest.fixture(scope='module')
 def host():
     return load_host()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def build(host, tri, order):
@@ -218,7 +199,7 @@ def test_beta_below_one_is_refused(host):
 def test_standalone_program_under_sanitizers(tmp_path):
     """The stand-alone program (its own main, nothing loaded into Python) built with AddressSanitizer + UBSan: the same meshes, their
     query points and the points on their surfaces, a NaN point among them, at beta = 2 and beta = 1."""
-    exe = _compile(os.path.join(OUT, 'dsdf_winding_host_asan'), ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined'])
+    exe = sanitized_program('dsdf_winding_host.cpp')
     for name, tri in O.MESHES.items():
         pts = np.concatenate([O.all_points(tri, len(name), n_random=2000), O.surface_points(tri, 0), np.float32([[np.nan, 0, 0]])])
         for beta in (2.0, 1.0):
@@ -226,9 +207,7 @@ def test_standalone_program_under_sanitizers(tmp_path):
             with open(fn, 'wb') as fh:
                 fh.write(np.asarray([tri.shape[0], pts.shape[0]], np.int32).tobytes() + np.float32(beta).tobytes())
                 fh.write(tri.tobytes() + pts.tobytes())
-            r = subprocess.run([exe, str(fn)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            assert r.returncode == 0, r.stdout
-            assert ' 0 mismatches' in r.stdout and 'runtime error' not in r.stdout and 'AddressSanitizer' not in r.stdout, r.stdout
+            run_case(exe, fn)
 
 
 def test_python_layer_checks_that_need_no_device():
