@@ -33,6 +33,7 @@
 //   k_mesh_closest, k_mesh_bvh_closest   closest point of a mesh: brute force and through the BVH             [dsdf_mesh.h, dsdf_bvh.h]
 //   k_mesh_winding, k_wind_*, k_mesh_bvh_winding   generalized winding number: exact sum, node moments, tree walk        [dsdf_winding.h]
 //   k_simplify_keys, k_simplify_mark, k_simplify_faces, k_simplify_cells   mesh simplification: vertex clustering with quadrics   [dsdf_simplify.h]
+//   k_cc_init, k_cc_hook, k_cc_flatten, k_mesh_face_measures   connected components of a mesh: lock-free union-find; face area / volume terms   [dsdf_components.h]
 //
 // wave = 64 lanes; one lane = one film sample, consecutive lanes = consecutive
 // samples of the same pixel (reference lane order, reparam.py:140-155), so for
@@ -2029,3 +2030,4 @@ int dsdf_kernel_timing_read(float *ms) {
 #include "dsdf_mesh.h"
 #include "dsdf_winding.h"
 #include "dsdf_simplify.h"
+#include "dsdf_components.h"

@@ -115,6 +115,8 @@ SYMBOLS = {
     'dsdf_simplify_mark': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'dsdf_simplify_emit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                      C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10),
+    'dsdf_mesh_components': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'dsdf_mesh_face_measures': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'dsdf_mesh_render_workspace_size': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'dsdf_mesh_render_forward': (C.c_int, [C.c_void_p, C.POINTER(DsdfParams), C.POINTER(DsdfCamera), C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(DsdfShading), C.c_void_p, C.c_void_p,

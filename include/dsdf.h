@@ -560,6 +560,27 @@ int dsdf_simplify_emit(const float *vertices, const int32_t *faces, int64_t n_fa
                        const int32_t *used, const int32_t *vertex_id, int32_t *faces_out, float *positions_out, float *normals_out,
                        float *colors_out, void *stream);
 
+/* ---- connected components of an indexed mesh: lock-free union-find over the index buffer (csrc/dsdf_components.h) ----
+ * An indexed mesh: faces F x 3 int32, every index in [0, V) (the caller's duty), 3 F < 2^31.
+ *   connected   two vertices are connected when a face names both: connection by shared vertex INDEX, not by shared edge (two triangles
+ *               that touch in one vertex are one component) and not by position.  A face with a repeated index connects its distinct ones.
+ *   label       label[v] = the smallest vertex index in v's component; a vertex that no face names is its own label.
+ *   numbering   (the caller's, from label) components are numbered 0 ... C - 1 in ascending order of their label, counting only
+ *               components with at least one face: face_component[f] in [0, C); vertex_component[v] in [0, C), or -1 for a vertex that no
+ *               face names.
+ *   measures    per face, every statement rounded on its own (no FMA): area = 0.5 |(p1 - p0) x (p2 - p0)|, vol = (p0 . (p1 x p2)) / 6; the
+ *               caller sums them per component (the sum of vol is a volume only for a closed component).
+ * dsdf_mesh_components makes three launches in stream order: label[v] = v; one lane per face, two unions (i0, i1), (i1, i2), each of which
+ * finds the two roots by walking label and hooks the larger under the smaller by compare-and-swap until both are one; label[v] = root(v).
+ * The result is an exact function of the input, whatever the order of the lanes.  `status` (1 int32, ZEROED by the caller): a walk or retry
+ * loop that exceeds V + 1 steps -- impossible on valid input -- ORs 1 into it and gives up; the caller reads it with the labels.
+ * n_faces = 0 still sets label[v] = v; n_vertices = 0 returns DSDF_OK without a launch.  dsdf_mesh_face_measures: n_faces = 0 likewise.
+ * Nothing here allocates or synchronises. */
+int dsdf_mesh_components(const int32_t *faces, int64_t n_faces, int n_vertices, int32_t *label /* V */,
+                         int32_t *status /* 1, zeroed by the caller */, void *stream);
+int dsdf_mesh_face_measures(const float *vertices, const int32_t *faces, int64_t n_faces, float *area /* F */, float *vol /* F */,
+                            void *stream);
+
 /* Trilinear lookup of a (vz, vy, vx, channels) fp32 volume on the unit cube, channels 1 or 3, at n points (n x 3, in the volume's frame):
  * out n x channels.  The value the direct integrator reads there (shading->albedo, ->roughness): texel centres (i + 0.5) / res, clamped
  * indices.  Bakes a reflectance volume onto the vertices of an extracted mesh (their WORLD-space positions: the volume lives in world
